@@ -6,13 +6,19 @@ packing, the query kernel, the RCCL all-reduce of the partial group-by tables (N
 host results.  Segments are generated in HBM before timing (synthetic data, seeded; see pinot_amd/synth.py).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload adanalytics|range_in|groupby1m|bitmap5|...]
+                  [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...       (one process per GPU, RCCL over xGMI)
 
-Prints ONE JSON line (rank 0) with the roofline of the dominant kernel (query_kernel: algorithmic bytes per
-launch / its HIP-event time) and the CPU baseline (oracle/pinot_cpu.c, Pinot's per-segment operators restated,
-timed on a bounded sample on this host).  The default N=1 run also measures BASELINE.json configs 2-4 and the
-SURVEY.md 8(d) variants (Zipf keys, inverted-indexed accountId) into a `workloads` sub-object, each with its own
-ms/step, roofline and CPU baseline.
+Prints ONE JSON line (rank 0).  A plain run does only what the headline figure needs: it generates the segments,
+warms up, times the K steps, writes the last step's results when --dump-outputs is given, and prints the line
+(metric, value, unit, ms_per_step, ...; roofline carries the kernel's name and its HIP-event time only).
+
+--full adds everything else: the roofline of the dominant kernel (query_kernel: algorithmic bytes per launch, from
+a statistics pass of its own, / its HIP-event time), the HBM residency, the CPU baseline (oracle/pinot_cpu.c,
+Pinot's per-segment operators restated, timed on a bounded sample on this host) with the GPU-vs-oracle parity
+checks, the full records in --full-out, and, in the N=1 run, BASELINE.json configs 2-4 and the SURVEY.md 8(d)
+variants (Zipf keys, inverted-indexed accountId) in a `workloads` sub-object, each with its own ms/step, roofline
+and CPU baseline.  --no-cpu-baseline / --no-check / --no-secondary drop parts of a --full run.
 """
 from __future__ import annotations
 
@@ -42,16 +48,22 @@ def parse_args(argv=None):
     ap.add_argument("--inflight", type=int, default=3,
                     help="queries in flight at N=1 (the host plans query i+1 while the GPU runs query i)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = Pinot default min(#seg, min(10, nproc/2))")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline bytes (a statistics pass), "
+                         "HBM residency, CPU baseline, parity checks, secondary workloads, the --full-out records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rows, every group, statistics) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the small GPU-vs-oracle check of this workload")
+    ap.add_argument("--no-check", action="store_true", help="skip the small GPU-vs-oracle check of this workload (--full)")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false",
-                    help="measure the headline workload only (default N=1 run: also configs 2-4 and variants)")
+                    help="measure the headline workload only (N=1 --full run: also configs 2-4 and variants)")
     ap.add_argument("--node", action="store_true",
                     help="drive --gpus devices from this one process through libpinotgpu's node combine "
                          "(pgpu_node_query_topk, RCCL inside the library: the one-JVM server's shape) instead of one "
                          "process per GPU")
     ap.add_argument("--full-out", default=os.environ.get("PGPU_BENCH_FULL", os.path.join("gpurun_out", "bench_full.json")),
-                    help="file for the full per-workload records (the stdout line carries a compact summary)")
+                    help="file for the full per-workload records of a --full run (the stdout line carries a compact "
+                         "summary)")
     return ap.parse_args(argv)
 
 
@@ -205,9 +217,10 @@ def kernel_label(ex, opts) -> str:
 
 
 def run_workload(name, ctx, args, world, rank, steps, warmup, segments, cpu_seconds, log, barrier, node=None):
-    """Generate the workload's segments in HBM, measure it, time the CPU baseline beside it; returns the full
-    record of one result (the compact line is built from it by compact_record).  `node` (a GpuNode) drives its
-    devices from this process; the segments are then sharded over the node's devices as over ranks."""
+    """Generate the workload's segments in HBM and measure it; with --full also its roofline bytes (a statistics
+    pass), HBM residency and the CPU baseline beside it.  Returns the full record of one result (the compact line
+    is built from it by compact_line) and the last timed step's result.  `node` (a GpuNode) drives its devices
+    from this process; the segments are then sharded over the node's devices as over ranks."""
     import torch
     from pinot_amd.combine import DistributedExecutor
     from pinot_amd.plan import GpuPlanMaker
@@ -233,9 +246,11 @@ def run_workload(name, ctx, args, world, rank, steps, warmup, segments, cpu_seco
     segs, seg_ids = segs_by_dev[0], ids_by_dev[0]
     gen_s = time.time() - t0
     log(f"{name}: generated {ndev} x {len(segs)} segments x {args.docs} docs in {gen_s:.1f}s")
-    hbm = resident_bytes(ctx, segs, nseg * args.docs)
-    log(f"{name}: resident {hbm['resident_bytes_per_gpu'] / 1e9:.2f} GB per GPU, {hbm['bytes_per_row']:.2f} B/row "
-        f"({hbm['forward_index_bytes_per_row']:.2f} forward index, {hbm['derived_bytes_per_row']:.2f} derived)")
+    hbm = None
+    if args.full:
+        hbm = resident_bytes(ctx, segs, nseg * args.docs)
+        log(f"{name}: resident {hbm['resident_bytes_per_gpu'] / 1e9:.2f} GB per GPU, {hbm['bytes_per_row']:.2f} B/row "
+            f"({hbm['forward_index_bytes_per_row']:.2f} forward index, {hbm['derived_bytes_per_row']:.2f} derived)")
     opts = dict(w.options)
     q = parse_sql(w.sql)
     if node is not None:
@@ -248,20 +263,25 @@ def run_workload(name, ctx, args, world, rank, steps, warmup, segments, cpu_seco
         pm = GpuPlanMaker(ctx, **plan_options(opts))
         ex = DistributedExecutor(pm)
     try:
-        algo_bytes, st, breakdown, read_bytes, read_breakdown = algorithmic_bytes(ex, pm, q, segs_by_dev, w,
-                                                                                  ids_by_dev, args.docs)
-        log(f"{name}: stats pass: {st.num_docs_scanned} matched, {algo_bytes / 1e9:.3f} GB algorithmic, "
-            f"{read_bytes / 1e9:.3f} GB read by the kernels, {st.kernel_ms:.3f} ms")
+        algo_bytes = breakdown = read_bytes = read_breakdown = None
+        if args.full:
+            algo_bytes, st, breakdown, read_bytes, read_breakdown = algorithmic_bytes(ex, pm, q, segs_by_dev, w,
+                                                                                      ids_by_dev, args.docs)
+            log(f"{name}: stats pass: {st.num_docs_scanned} matched, {algo_bytes / 1e9:.3f} GB algorithmic, "
+                f"{read_bytes / 1e9:.3f} GB read by the kernels, {st.kernel_ms:.3f} ms")
         ms_per_step, avg_kernel_ms, result = measure(ex, q, segs, steps, warmup, args.inflight, world, barrier)
+        if not args.full:
+            st = ex.last_stats  # of the last timed query
         rows_per_gpu = nseg * args.docs
         # per GPU: this rank's (or, in node mode, the average device's) algorithmic bytes over the span of the
         # kernels of one query on its stream (the slowest device's in node mode)
-        achieved = algo_bytes / ndev / (avg_kernel_ms * 1e-3) / 1e9
-        log(f"{name}: timed: {ms_per_step:.3f} ms/step, kernels {avg_kernel_ms:.3f} ms, {achieved:.0f} GB/s per GPU")
+        achieved = algo_bytes / ndev / (avg_kernel_ms * 1e-3) / 1e9 if args.full else None
+        log(f"{name}: timed: {ms_per_step:.3f} ms/step, kernels {avg_kernel_ms:.3f} ms" +
+            (f", {achieved:.0f} GB/s per GPU" if args.full else ""))
         cpu = check = None
-        if rank == 0 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and not args.no_cpu_baseline:
             cpu, check = cpu_baseline(ctx, w, q, opts, args, cpu_seconds, segs)
-        traffic, traffic_src = _pmc_traffic(name)
+        traffic, traffic_src = _pmc_traffic(name) if args.full else (None, None)
         return {
             "value": rows_per_gpu * world * ndev / (ms_per_step * 1e-3),
             "ms_per_step": ms_per_step,
@@ -276,9 +296,10 @@ def run_workload(name, ctx, args, world, rank, steps, warmup, segments, cpu_seco
                                       (f"segments sharded over {world} GPU(s), one process each; partial tables "
                                        "merged over RCCL (torch.distributed)")},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                         "frac": achieved / HBM_PEAK_GBS if args.full else None, "traffic": traffic,
+                         "traffic_source": traffic_src,
                          "kernel": kernel_label(ex, opts),
-                         "algorithmic_bytes_per_launch": algo_bytes / ndev,
+                         "algorithmic_bytes_per_launch": algo_bytes / ndev if args.full else None,
                          "kernel_ms_avg": avg_kernel_ms,
                          "kernel_ms_definition": "HIP events on the query stream around every kernel that reads "
                                                  "the segments (leaf bitmaps, query kernel, group-by phases, "
@@ -293,14 +314,57 @@ def run_workload(name, ctx, args, world, rank, steps, warmup, segments, cpu_seco
             "parity_check": check,
             "hbm": hbm,
             "setup_s": round(gen_s, 1),
-        }
+        }, result
     finally:
         for ss in segs_by_dev:
             for s in ss:
                 s.release()
 
 
-# Secondary workloads measured after the headline in the default run (BASELINE.json configs 2-4 and the SURVEY 8(d)
+DUMP_LIMIT_BYTES = 60_000_000  # --dump-outputs writes at most this much array data in all (files: under 64 MB)
+DUMP_SAMPLE_SEED = 20
+
+
+def output_arrays(result):
+    """What a caller of the timed path receives from one query, as float64 arrays: `rows` (the SELECT-ordered
+    rows after ORDER BY / LIMIT), `group_rows` (group-by: every group, ascending by key) or `aggregation_result`
+    (aggregation-only), and `stats` (numDocsScanned, numEntriesScannedPostFilter, numTotalDocs,
+    numSegmentsProcessed, numSegmentsMatched).  A missing value (MIN / MAX of no docs) is NaN."""
+    import numpy as np
+
+    def table(rows):
+        rows = list(rows or [])
+        width = len(rows[0]) if rows else 0
+        return np.array([[np.nan if v is None else float(v) for v in r] for r in rows],
+                        dtype=np.float64).reshape(len(rows), width)
+
+    st = result.stats
+    out = {"stats": np.array([st.num_docs_scanned, st.num_entries_scanned_post_filter, st.num_total_docs,
+                              st.num_segments_processed, st.num_segments_matched], dtype=np.float64),
+           "rows": table(result.rows)}
+    if result.query.group_by:
+        out["group_rows"] = table(result.group_rows)
+    elif result.aggregation_result is not None:
+        out["aggregation_result"] = table([result.aggregation_result])[0]
+    return out
+
+
+def dump_outputs(directory, result):
+    """Write output_arrays(result) as <directory>/<name>.npy.  An array above its share of DUMP_LIMIT_BYTES is
+    cut to a fixed, seeded sample of its rows (in their order), the same sample on every run."""
+    import numpy as np
+
+    arrays = output_arrays(result)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            keep = share // max(1, a.nbytes // len(a))
+            a = a[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+# Secondary workloads measured after the headline in the --full run (BASELINE.json configs 2-4 and the SURVEY 8(d)
 # variants): (name, steps, warmup, segments per GPU or 0 = the workload's own, CPU sample seconds)
 SECONDARY = [("range_in", 10, 2, 0, 3.0), ("groupby1m", 5, 1, 0, 3.0), ("bitmap5", 10, 2, 0, 3.0),
              ("groupby1m_zipf", 5, 1, 0, 3.0), ("adanalytics_inv", 10, 2, 0, 3.0), ("adanalytics_exact", 10, 2, 0, 2.0),
@@ -338,8 +402,9 @@ def compact_workload(rec):
 
 
 def compact_line(head, workloads, args, n_gpus):
-    """The ONE stdout JSON line: the headline with roofline and cpu_baseline, the secondary workloads as a compact
-    map; the full records go to --full-out."""
+    """The ONE stdout JSON line: the headline with roofline and cpu_baseline (both filled by --full; a plain run's
+    roofline names the kernel and its time only), the secondary workloads as a compact map; the full records of a
+    --full run go to --full-out."""
     chk = head.get("parity_check")
     cfg = head["config"]
     line = {
@@ -363,7 +428,7 @@ def compact_line(head, workloads, args, n_gpus):
         "cpu_baseline": compact_cpu(head.get("cpu_baseline")),
         "parity_ok": None if chk is None else bool(chk.get("ok")),
         "matched_docs_per_gpu": head["result"]["matched_docs_per_gpu"],
-        "full_records": args.full_out,
+        "full_records": args.full_out if args.full else None,
     }
     if workloads:
         line["workloads"] = {k: compact_workload(v) for k, v in workloads.items()}
@@ -458,24 +523,29 @@ def main(argv=None):
         if world > 1:
             dist.barrier()
 
-    head = run_workload(args.workload, ctx, args, world, rank, args.steps, args.warmup, args.segments,
-                        args.cpu_seconds, log, barrier, node=node)
+    head, result = run_workload(args.workload, ctx, args, world, rank, args.steps, args.warmup, args.segments,
+                                args.cpu_seconds, log, barrier, node=node)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, result)
+    del result
     workloads = {}
-    if args.secondary and world == 1 and node is None and args.workload == "adanalytics":
+    if args.full and args.secondary and world == 1 and node is None and args.workload == "adanalytics":
         for name, steps, warmup, nseg, cpu_s in SECONDARY:
             try:
-                workloads[name] = run_workload(name, ctx, args, world, rank, steps, warmup, nseg, cpu_s, log, barrier)
+                workloads[name], _ = run_workload(name, ctx, args, world, rank, steps, warmup, nseg, cpu_s, log,
+                                                  barrier)
             except Exception as e:  # a secondary workload never hides the headline line
                 log(f"{name}: failed: {e!r}")
                 workloads[name] = {"error": repr(e)}
     if rank == 0:
-        full = {"headline": head, "workloads": workloads}
-        try:
-            os.makedirs(os.path.dirname(os.path.abspath(args.full_out)), exist_ok=True)
-            with open(args.full_out, "w") as f:
-                json.dump(full, f, default=float, indent=1)
-        except OSError as e:
-            log(f"full records not written: {e!r}")
+        if args.full:
+            full = {"headline": head, "workloads": workloads}
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(args.full_out)), exist_ok=True)
+                with open(args.full_out, "w") as f:
+                    json.dump(full, f, default=float, indent=1)
+            except OSError as e:
+                log(f"full records not written: {e!r}")
         line = compact_line(head, workloads, args, head["n_gpus"])
         text = json.dumps(line, default=float, separators=(",", ":"))
         if len(text) > LINE_LIMIT:  # never let the line outgrow the driver's stdout tail

@@ -11,7 +11,7 @@ for wl in ${WLS:-groupby1m_zipf groupby1m}; do
     name=${wl}_hot$hot
     if [ $hot = 0 ]; then export PGPU_NO_HOTKEYS=1; else unset PGPU_NO_HOTKEYS; fi
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$name" -o run -- \
-      python3 $R/bench.py --no-cpu-baseline --no-check --no-secondary --workload $wl --steps ${STEPS:-10} --warmup 2 \
+      python3 $R/bench.py --full --no-cpu-baseline --no-check --no-secondary --workload $wl --steps ${STEPS:-10} --warmup 2 \
       --full-out "$OUT/$name.json" > "$OUT/$name.log" 2>&1 || { echo "trace $name failed rc=$?"; tail -5 "$OUT/$name.log"; exit 1; }
     grep -h '"metric"' "$OUT/$name.log" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', round(d['ms_per_step'],3), round(d['roofline']['kernel_ms_avg'],3), round(d['roofline']['frac'],3))"
   done

@@ -13,7 +13,7 @@ echo "tests rc=$rc"; tail -3 "$OUT/gpu_tests.log"
 # a failed or faulted test run ends the GPU work of this call (rc 5: no tests selected is fine)
 if [ $rc -ne 0 ] && [ $rc -ne 5 ]; then exit $rc; fi
 cd /tmp && export TMPDIR=/tmp
-BENCH="$R/bench.py --no-cpu-baseline --no-check --no-secondary"
+BENCH="$R/bench.py --full --no-cpu-baseline --no-check --no-secondary"
 for wl in ${WLS:-range_in bitmap5 adanalytics_exact}; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$wl" -o run -- \
     python3 $BENCH --workload $wl --steps ${STEPS:-10} --warmup 2 > "$OUT/$wl.log" 2>&1 || { echo "trace $wl failed rc=$?"; tail -5 "$OUT/$wl.log"; exit 1; }

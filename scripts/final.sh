@@ -10,7 +10,7 @@ timeout -k 10 720 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout
 rc=$?
 echo "tests rc=$rc"; tail -3 "$OUT/gpu_tests.log"
 if [ $rc -ne 0 ]; then exit $rc; fi
-timeout -k 10 900 python -u bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
+timeout -k 10 900 python -u bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
 rc=$?
 echo "bench rc=$rc"; grep '"metric"' "$OUT/bench.log" | tail -1 | cut -c1-400
 exit $rc

@@ -5,7 +5,7 @@ set -u
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 TAG=$1; WLS=$2; KNOB=${3:-}
 OUT=$R/gpurun_out/$TAG; mkdir -p "$OUT"
-BENCH="$R/bench.py --no-cpu-baseline --no-check --no-secondary"
+BENCH="$R/bench.py --full --no-cpu-baseline --no-check --no-secondary"
 for wl in $WLS; do
   for variant in base knob; do
     if [ $variant = knob ] && [ -z "$KNOB" ]; then continue; fi

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/$TAG; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for wl in $WLS; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$wl" -o run -- \
-    python3 $R/bench.py --no-cpu-baseline --no-check --no-secondary --workload $wl --steps ${STEPS:-20} --warmup 3 \
+    python3 $R/bench.py --full --no-cpu-baseline --no-check --no-secondary --workload $wl --steps ${STEPS:-20} --warmup 3 \
     --full-out "$OUT/$wl.json" > "$OUT/$wl.log" 2>&1 || { echo "trace $wl failed rc=$?"; tail -5 "$OUT/$wl.log"; exit 1; }
   grep -h "timed:" "$OUT/$wl.log" | tail -1
 done

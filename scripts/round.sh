@@ -13,13 +13,13 @@ echo "tests rc=$rc"; tail -3 "$OUT/gpu_tests.log"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ] && [ $rc -ne 5 ]; then exit $rc; fi
 TRC=$rc
 if [ "${BENCH:-1}" = "1" ]; then
-  timeout -k 10 600 python -u bench.py --full-out "$OUT/bench_full.json" ${BENCH_ARGS:-} > "$OUT/bench.out" 2> "$OUT/bench.err"
+  timeout -k 10 600 python -u bench.py --full --full-out "$OUT/bench_full.json" ${BENCH_ARGS:-} > "$OUT/bench.out" 2> "$OUT/bench.err"
   rc=$?
   echo "bench rc=$rc"; wc -c "$OUT/bench.out"; tail -c 600 "$OUT/bench.out"
   if [ $rc -ne 0 ]; then tail -5 "$OUT/bench.err"; exit $rc; fi
 fi
 if [ "${NODE:-0}" = "1" ]; then
-  timeout -k 10 300 python -u bench.py --node --gpus 1 --no-secondary --steps 300 --full-out "$OUT/node_full.json" > "$OUT/node.out" 2> "$OUT/node.err"
+  timeout -k 10 300 python -u bench.py --full --node --gpus 1 --no-secondary --steps 300 --full-out "$OUT/node_full.json" > "$OUT/node.out" 2> "$OUT/node.err"
   rc=$?
   echo "node rc=$rc"; tail -c 400 "$OUT/node.out"
   if [ $rc -ne 0 ]; then tail -5 "$OUT/node.err"; exit $rc; fi

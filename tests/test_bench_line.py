@@ -61,6 +61,75 @@ def test_compact_line_fits_the_driver_tail():
     assert back["workloads"]["broken"]["error"].startswith("RuntimeError(")
 
 
+def plain_record(name):
+    """run_workload's record without --full: nothing that takes a run of its own is filled."""
+    rec = canned_record(name)
+    rec["roofline"].update({k: None for k in ("achieved", "frac", "traffic", "traffic_source",
+                                              "algorithmic_bytes_per_launch", "bytes_breakdown", "bytes_read_model",
+                                              "bytes_read_breakdown")})
+    rec.update({"cpu_baseline": None, "parity_check": None, "hbm": None})
+    return rec
+
+
+def test_plain_run_line_keeps_the_headline_fields():
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not args.full and args.dump_outputs is None
+    back = json.loads(json.dumps(bench.compact_line(plain_record("adanalytics"), {}, args, 1), default=float))
+    assert back["metric"] == bench.METRIC and back["unit"] == "rows/s" and back["dtype"] == "int64"
+    assert back["higher_is_better"] is True
+    assert back["value"] == pytest.approx(3.3e12) and back["ms_per_step"] == pytest.approx(0.3037)
+    assert back["steps"] == 7 and back["warmup"] == 2
+    assert set(back["roofline"]) == set(bench.ROOFLINE_KEYS)
+    assert back["roofline"]["kernel"] == "query_kernel_rdirect" and back["roofline"]["frac"] is None
+    assert back["cpu_baseline"] is None and back["parity_ok"] is None and back["full_records"] is None
+    assert "workloads" not in back
+    assert bench.parse_args(["--full"]).full
+
+
+class _Result:
+    """The fields of a QueryResult that --dump-outputs reads."""
+
+    def __init__(self, group_by, rows, group_rows=None, aggregation_result=None):
+        from types import SimpleNamespace
+        self.query = SimpleNamespace(group_by=group_by)
+        self.stats = SimpleNamespace(num_docs_scanned=11, num_entries_scanned_post_filter=33, num_total_docs=1000,
+                                     num_segments_processed=2, num_segments_matched=1)
+        self.rows, self.group_rows, self.aggregation_result = rows, group_rows, aggregation_result
+
+
+def test_dump_outputs_writes_float64_arrays(tmp_path):
+    import numpy as np
+    groups = [(k, float(k) * 1.5, None if k == 3 else k + (1 << 40)) for k in range(5)]
+    bench.dump_outputs(str(tmp_path / "g"), _Result(["k"], groups[:2], group_rows=groups))
+    got = {f: np.load(tmp_path / "g" / f) for f in sorted(os.listdir(tmp_path / "g"))}
+    assert sorted(got) == ["group_rows.npy", "rows.npy", "stats.npy"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["stats.npy"].tolist() == [11, 33, 1000, 2, 1]
+    assert got["rows.npy"].shape == (2, 3) and got["group_rows.npy"].shape == (5, 3)
+    assert got["group_rows.npy"][4].tolist() == [4.0, 6.0, float(4 + (1 << 40))]
+    assert np.isnan(got["group_rows.npy"][3, 2])
+    bench.dump_outputs(str(tmp_path / "a"), _Result([], [(7, 2.5)], aggregation_result=[7, 2.5]))
+    assert sorted(os.listdir(tmp_path / "a")) == ["aggregation_result.npy", "rows.npy", "stats.npy"]
+    assert np.load(tmp_path / "a" / "aggregation_result.npy").tolist() == [7.0, 2.5]
+    bench.dump_outputs(str(tmp_path / "e"), _Result(["k"], [], group_rows=[]))  # no group matched
+    assert np.load(tmp_path / "e" / "group_rows.npy").shape == (0, 0)
+
+
+def test_dump_outputs_samples_a_large_output(tmp_path, monkeypatch):
+    """An output above its share of the size limit is cut to the same seeded sample of its rows on every run."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * 24 * 100)  # three arrays: 100 rows of 3 doubles each
+    groups = [(k, k * 2, k * 3) for k in range(1000)]
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), _Result(["k"], groups[:10], group_rows=groups))
+    x, y = (np.load(tmp_path / d / "group_rows.npy") for d in ("x", "y"))
+    assert x.shape == (100, 3) and np.array_equal(x, y)
+    assert np.all(np.diff(x[:, 0]) > 0) and np.array_equal(x[:, 1], x[:, 0] * 2)  # whole rows, in their order
+    assert np.load(tmp_path / "x" / "rows.npy").shape == (10, 3)
+    total = sum(os.path.getsize(tmp_path / "x" / f) for f in os.listdir(tmp_path / "x"))
+    assert total <= 3 * 24 * 100 + 3 * 128  # the arrays plus the .npy headers
+
+
 def test_gpus_spawns_one_rank_per_gpu(monkeypatch):
     """`bench.py --gpus 4` without a launcher starts four rank processes with the torch.distributed environment
     (WORLD_SIZE = 4, ranks 0..3, one port, 127.0.0.1), before touching the GPU."""
