@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PGPU_ABI_VERSION 12
+#define PGPU_ABI_VERSION 13
 
 /* ---- status codes ---------------------------------------------------------------------------------------- */
 #define PGPU_OK 0
@@ -269,6 +269,8 @@ typedef struct {
 #define PGPU_AGG_MIN 2   /* MinAggregationFunction.java:55-138, empty = +inf */
 #define PGPU_AGG_MAX 3   /* MaxAggregationFunction.java:55-138, empty = -inf */
 #define PGPU_AGG_AVG 4   /* AvgAggregationFunction.java:58-190 + AvgPair */
+/* (fn values above PGPU_AGG_AVG are PGPU_E_UNSUPPORTED.  DISTINCTCOUNT is no descriptor function: it is a GROUP BY on
+ * the column, folded at collect -- pgpu_query_collect_fold below.) */
 
 typedef struct {
   int32_t fn;
@@ -340,6 +342,10 @@ typedef struct {
  * forward-index entries, which equals the reference's except under leap-frogging iterators (an AND of several
  * scan leaves, an OR / NOT advanced by a parent AND); pgpu_query_stats.filter_stats_exact tells which. */
 #define PGPU_Q_EXACT_FILTER_STATS 32ull
+/* The submitted query's table will be collected by pgpu_query_collect_fold: pgpu_query_submit* leaves it on the
+ * device as it is -- no copy of a small table to the host, no compaction behind the kernels -- since only its fold
+ * comes back.  pgpu_query_collect(_topk) still works on such a query (compacting at collect). */
+#define PGPU_Q_FOLD 64ull
 
 /* ---- partial-result table ----------------------------------------------------------------------------------
  * A query produces a dense table over G = prod(group_cardinalities) keys (G = 1 for aggregation only), laid out
@@ -511,6 +517,45 @@ int pgpu_table_topk(pgpu_context* ctx, const pgpu_table_layout* layout, const vo
 /* pgpu_query_collect returning only the best groups by `order` (NULL = all, as pgpu_query_collect). */
 int pgpu_query_collect_topk(pgpu_query* query, const pgpu_topk* order, int64_t* out_keys, int64_t* out_cells,
                             uint64_t capacity, uint64_t* out_num_groups, pgpu_query_stats* out_stats);
+
+/* ---- DISTINCTCOUNT: fold of a group table over its last group column ------------------------------------------
+ * DISTINCTCOUNT(c) (DistinctCountAggregationFunction.java:66-250 aggregates a bitmap of c's dictionary ids per group,
+ * :252-310 merges the value sets and extracts their size as an INT) with group columns g_1..g_n runs as the query
+ * GROUP BY g_1..g_n, c -- c last, so by the key formula above key = g + inner * cid with inner = prod card(g_j)
+ * (1 for aggregation only) and cid the id of c in its global dictionary.  Which (g, cid) cells are occupied is the
+ * distinct set; the fold reduces that table over cid into a dense table over the `inner` keys g:
+ *   every section of the input, in the same order, combined over cid by its own section_op (cells of count 0
+ *     contribute nothing, so these equal, cell for cell, the table GROUP BY g_1..g_n alone produces; bit for bit
+ *     for every int64 section, a float64 SUM section up to the order of its adds);
+ *   one more int64 SUM section: the number of cid whose cell has count > 0 -- the distinct count.
+ * pgpu_fold_layout_of (host only) describes the folded table: dense, num_keys = inner_keys, the sections and
+ * aggregation entries of `in` copied, and section in->num_sections (PGPU_RED_SUM_I64) appended, also described as
+ * the first unused aggregation entry n (agg_section = that section, agg_value_type = PGPU_LONG, agg_sum_parts = 1,
+ * agg_sum_exp = 0; an entry is unused when its section and value type are both 0 -- pgpu_table_layout_of gives a
+ * COUNT the type -1 and any other aggregation its section -- so n = the query's num_aggs), so that
+ * pgpu_table_compact and pgpu_table_topk work on a folded table unchanged: an order on the distinct count is
+ * {PGPU_TOPK_AGG, PGPU_AGG_SUM, agg_index = n}.
+ *   PGPU_E_INVALID    : inner_keys = 0, or a dense `in` whose num_keys is no multiple of inner_keys
+ *   PGPU_E_UNSUPPORTED: two key words, inner_keys > 2^26 (the most rows a collect returns), no section or
+ *                       aggregation entry left */
+#define PGPU_FOLD_MAX_KEYS (1ull << 26)
+int pgpu_fold_layout_of(const pgpu_table_layout* in, uint64_t inner_keys, pgpu_table_layout* out);
+/* Fold the table `dev_table` of layout `in_layout` into caller memory `dev_out` (out_bytes >= pgpu_table_bytes of
+ * the folded layout): a table -> table operation like pgpu_table_topk, enqueued on `stream` (hipStream_t; NULL =
+ * HIP's default stream) without synchronising.  dev_out is first set to every section's identity.  Dense input: the
+ * cell index is the key.  One-word hash input: a slot is occupied when its count > 0 and its key is word 0 (int64
+ * index num_sections * num_keys + slot); g = key % inner_keys.  The call a multi-GPU combine makes on its reduced
+ * table, which is why it is separate from the collect below. */
+int pgpu_table_fold(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
+                    uint64_t inner_keys, void* dev_out, uint64_t out_bytes);
+/* pgpu_query_collect_topk for a submitted GROUP BY g_1..g_n, c query: waits (PGPU_E_CANCELLED / PGPU_E_TIMEOUT pass
+ * through and nothing is folded), folds the query's table on its workspace stream into workspace memory, compacts
+ * the folded table -- or keeps its best rows by `order`, which refers to the folded layout (NULL = all) -- copies
+ * the rows out (out_keys = the keys over g, out_cells = capacity x folded num_sections) and releases the query
+ * (also on error).  *out_layout (may be NULL) receives the folded layout.  Submit such a query with PGPU_Q_FOLD. */
+int pgpu_query_collect_fold(pgpu_query* query, uint64_t inner_keys, const pgpu_topk* order, int64_t* out_keys,
+                            int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
+                            pgpu_query_stats* out_stats, pgpu_table_layout* out_layout);
 
 /* Single-GPU asynchronous form (the combine operator of one server: BaseCombineOperator.getNextBlock submits the
  * segments' work and blocks in mergeResults, core/operator/combine/BaseCombineOperator.java:79-146):

@@ -37,13 +37,15 @@ PGPU_AGG_COUNT, PGPU_AGG_SUM, PGPU_AGG_MIN, PGPU_AGG_MAX, PGPU_AGG_AVG = range(5
 PGPU_RED_SUM_I64, PGPU_RED_SUM_F64, PGPU_RED_MIN_I64, PGPU_RED_MAX_I64 = range(4)
 PGPU_Q_STATS, PGPU_Q_PARTITION, PGPU_Q_PART_SPILL, PGPU_Q_SUM_SPLIT, PGPU_Q_HASH = 1, 2, 4, 8, 16
 PGPU_Q_EXACT_FILTER_STATS = 32
+PGPU_Q_FOLD = 64  # the table comes back through pgpu_query_collect_fold only
 PGPU_KEYS_DENSE, PGPU_KEYS_HASH = 0, 1
 PGPU_PART_BITS = 21  # split integer SUM: three sections of 21-bit parts (include/pinot_gpu.h)
 PGPU_SUM_EXP_F64 = 32767  # pgpu_table_layout.agg_sum_exp of a float64 SUM section
 PGPU_SUM_EXP_ZERO = -32767  # ... of a fixed-point SUM over a column holding only zeros
 PGPU_MAX_FIXED_PARTS = 6  # widest fixed-point window (21-bit parts) of a floating SUM
 PGPU_FIXED_TOL_BITS = 40
-ABI_VERSION = 12
+PGPU_FOLD_MAX_KEYS = 1 << 26  # most inner keys of a fold (pgpu_fold_layout_of)
+ABI_VERSION = 13
 
 
 class PinotGpuError(RuntimeError):
@@ -198,6 +200,11 @@ SIGNATURES = [
                                   C.POINTER(C.c_int64), C.c_uint64, C.POINTER(C.c_uint64)]),
     ("pgpu_query_collect_topk", C.c_int, [_P, C.POINTER(TopK), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                           C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(QueryStats)]),
+    ("pgpu_fold_layout_of", C.c_int, [C.POINTER(TableLayout), C.c_uint64, C.POINTER(TableLayout)]),
+    ("pgpu_table_fold", C.c_int, [_P, C.POINTER(TableLayout), _P, _P, C.c_uint64, _P, C.c_uint64]),
+    ("pgpu_query_collect_fold", C.c_int, [_P, C.c_uint64, C.POINTER(TopK), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                          C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(QueryStats),
+                                          C.POINTER(TableLayout)]),
     ("pgpu_query_submit", C.c_int, [_P, C.POINTER(QueryDesc), C.POINTER(_P)]),
     ("pgpu_query_collect", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_uint64,
                                      C.POINTER(C.c_uint64), C.POINTER(QueryStats)]),

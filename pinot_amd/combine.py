@@ -465,6 +465,7 @@ class DistributedExecutor:
         plans and reduces query i while the GPU runs query i+1)."""
         if self.world == 1:
             return self.pm.submit(query, segments)
+        _refuse_distinct(query)  # (on every rank alike, before any collective)
         import torch
         if not segments:
             raise ValueError("every rank needs at least one segment")
@@ -706,6 +707,7 @@ class DistributedExecutor:
             res = self.pm.execute(query, segments)
             self.last_stats = res.stats
             return res
+        _refuse_distinct(query)  # (on every rank alike, before any collective)
         if has_mv_aggregations(query):
             # *MV aggregations over the multi-value columns' row columns (pinot_amd/mv.py), raised on rank 0
             check_group_columns(query, segments)
@@ -719,6 +721,14 @@ class DistributedExecutor:
             results = [self.collect(pq) for pq in pending]
             return None if results[0] is None else merge_filtered(query, parts, results)
         return self.collect(self.submit(query, segments))
+
+
+def _refuse_distinct(query: QueryContext) -> None:
+    """DISTINCTCOUNT across ranks needs the fold after the reduce (pgpu_table_fold on the reduced table), which the
+    multi-GPU combines do not do yet: the server keeps its CPU plan."""
+    if any(a.function == "DISTINCTCOUNT" for a in query.aggregations):
+        raise _lib.UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED,
+                                        "DISTINCTCOUNT is not served by the multi-GPU combine (DistributedExecutor)")
 
 
 class _DistPending:

@@ -66,6 +66,9 @@ hipError_t pgpu_gdict_sort_unique(const void* vals, int32_t dtype, int64_t n, ui
                                   uint64_t* uniq, uint32_t* d_card, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t pgpu_gdict_encode(const uint64_t* keys, int64_t n, const uint64_t* uniq, int32_t card, int32_t dtype,
                              int bits, void* dict, uint32_t* ids, uint32_t* words, int64_t nwords, hipStream_t st);
+// fold of a group table over its last group column (pgpu_fold.hip)
+hipError_t pgpu_launch_fold(const int64_t* in, uint64_t N, int32_t nsec, const int32_t* ops, bool hash, uint64_t inner,
+                            int64_t* out, int num_cus, hipStream_t st);
 
 namespace {
 
@@ -286,7 +289,9 @@ struct Workspace {
   DevMem rawbits;                      // match bitmaps of the raw-value leaves (rawpred_kernel)
   DevMem rkctab;                       // query_kernel_rkey: container record per (leaf, id, key)
   DevMem tk_keys, tk_state;            // pgpu_table_topk: per-row order keys, radix-select state + histogram
+  DevMem fold;                         // pgpu_query_collect_fold: the folded table
   PinnedMem h_arena, h_stats, h_total, h_table, h_segcnt, h_leafbits, h_segany, h_fsment;
+  PinnedMem h_fold;                    // pgpu_query_collect_fold: a small folded table, compacted on the host
   DevMem d_cancel;                     // cancel word (DevParams::cancel): = the query's generation -> stop
   PinnedMem h_cancel;                  // its source for pgpu_query_cancel's copy-engine write
   uint32_t cancel_gen = 0;
@@ -4120,6 +4125,111 @@ int pgpu_table_topk(pgpu_context* ctx, const pgpu_table_layout* layout, const vo
   return rc;
 }
 
+// ---- DISTINCTCOUNT: fold of a GROUP BY g, c table over c (include/pinot_gpu.h; kernels in pgpu_fold.hip) ------------
+int pgpu_fold_layout_of(const pgpu_table_layout* in, uint64_t inner_keys, pgpu_table_layout* out) {
+  if (!in || !out) return fail(PGPU_E_INVALID, "null argument");
+  if (inner_keys == 0) return fail(PGPU_E_INVALID, "fold over 0 inner keys");
+  if (in->num_sections < 1 || in->num_sections > PGPU_MAX_SECTIONS)
+    return fail(PGPU_E_INVALID, "table of %d sections", in->num_sections);
+  const bool hash = in->key_kind == PGPU_KEYS_HASH;
+  if (!hash && in->num_keys % inner_keys != 0)
+    return fail(PGPU_E_INVALID, "%llu keys are no multiple of %llu inner keys", (unsigned long long)in->num_keys,
+                (unsigned long long)inner_keys);
+  if (hash && in->key_words == 2) return fail(PGPU_E_UNSUPPORTED, "fold of a table with two key words");
+  if (inner_keys > PGPU_FOLD_MAX_KEYS)
+    return fail(PGPU_E_UNSUPPORTED, "fold into %llu keys (more than a collect returns)", (unsigned long long)inner_keys);
+  if (in->num_sections + 1 > PGPU_MAX_SECTIONS)
+    return fail(PGPU_E_UNSUPPORTED, "no section left for the distinct count (%d in use)", in->num_sections);
+  // the first unused aggregation entry: all zero (a COUNT has value type -1, any other aggregation its section)
+  int n = 16;
+  while (n > 0 && in->agg_section[n - 1] == 0 && in->agg_value_type[n - 1] == 0) --n;
+  if (n >= 16) return fail(PGPU_E_UNSUPPORTED, "no aggregation entry left for the distinct count");
+  pgpu_table_layout F = *in;
+  F.num_keys = inner_keys;
+  F.key_kind = PGPU_KEYS_DENSE;
+  F.key_words = 1;
+  F.section_op[F.num_sections] = PGPU_RED_SUM_I64;
+  F.agg_section[n] = F.num_sections;
+  F.agg_value_type[n] = PGPU_LONG;
+  F.agg_sum_parts[n] = 1;
+  F.agg_sum_exp[n] = 0;
+  F.num_sections += 1;
+  *out = F;
+  return PGPU_OK;
+}
+
+int pgpu_table_fold(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
+                    uint64_t inner_keys, void* dev_out, uint64_t out_bytes) {
+  if (!ctx || !in_layout || !dev_table || !dev_out) return fail(PGPU_E_INVALID, "null argument");
+  pgpu_table_layout F;
+  const int rc = pgpu_fold_layout_of(in_layout, inner_keys, &F);
+  if (rc) return rc;
+  if (out_bytes < pgpu_table_bytes(&F))
+    return fail(PGPU_E_INVALID, "folded table needs %llu bytes, %llu given", (unsigned long long)pgpu_table_bytes(&F),
+                (unsigned long long)out_bytes);
+  if (in_layout->num_keys == 0) return fail(PGPU_E_INVALID, "empty table");
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(pgpu_launch_fold((const int64_t*)dev_table, in_layout->num_keys, in_layout->num_sections,
+                           in_layout->section_op, in_layout->key_kind == PGPU_KEYS_HASH, inner_keys,
+                           (int64_t*)dev_out, ctx->num_cus, (hipStream_t)stream));
+  return PGPU_OK;
+}
+
+int pgpu_query_collect_fold(pgpu_query* qq, uint64_t inner_keys, const pgpu_topk* order, int64_t* out_keys,
+                            int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
+                            pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
+  if (!qq || !qq->tws || !out_num_groups) return fail(PGPU_E_INVALID, "query was not submitted");
+  // (a cancelled or timed-out query returns here: nothing is folded)
+  int rc = pgpu_query_wait(qq, out_stats);
+  pgpu_table_layout F;
+  if (rc == PGPU_OK) rc = pgpu_fold_layout_of(&qq->layout, inner_keys, &F);
+  if (rc == PGPU_OK) {
+    // the table is complete (waited above): fold and compact it on the query's own workspace stream
+    Workspace* ws = qq->ws;
+    const pgpu_table_layout& L = qq->layout;
+    hipError_t e = ws->fold.ensure(pgpu_table_bytes(&F) + 16, qq->ctx->mpool, ws->stream);
+    if (e == hipSuccess)
+      e = pgpu_launch_fold((const int64_t*)qq->tws->table.p, L.num_keys, L.num_sections, L.section_op,
+                           L.key_kind == PGPU_KEYS_HASH, inner_keys, (int64_t*)ws->fold.p, qq->ctx->num_cus, ws->stream);
+    if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table fold: %s", hipGetErrorString(e));
+  }
+  const bool trim = order && order->k > 0 && inner_keys > order->k;
+  if (rc == PGPU_OK && !trim && pgpu_table_bytes(&F) <= (8u << 20)) {
+    // a small folded table with nothing to trim comes back whole into pinned host memory and is compacted here,
+    // as pgpu_query_collect does with a small table: one synchronisation
+    Workspace* ws = qq->ws;
+    const uint64_t fb = pgpu_table_bytes(&F);
+    hipError_t e = ws->h_fold.ensure(fb);
+    if (e == hipSuccess) e = hipMemcpyAsync(ws->h_fold.p, ws->fold.p, fb, hipMemcpyDeviceToHost, ws->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
+    if (e != hipSuccess) {
+      rc = fail(PGPU_E_HIP, "folded table copy: %s", hipGetErrorString(e));
+    } else {
+      const int64_t* t = (const int64_t*)ws->h_fold.p;
+      const int nsec = F.num_sections;
+      uint64_t n = 0;
+      for (uint64_t k = 0; k < inner_keys; ++k) {
+        if (t[k] <= 0) continue;
+        if (n < capacity) {
+          out_keys[n] = (int64_t)k;
+          for (int sc = 0; sc < nsec; ++sc) out_cells[n * nsec + sc] = t[(size_t)sc * inner_keys + k];
+        }
+        ++n;
+      }
+      *out_num_groups = n;
+      if (n > capacity)
+        rc = fail(PGPU_E_INVALID, "%llu non-empty groups exceed capacity %llu", (unsigned long long)n,
+                  (unsigned long long)capacity);
+    }
+  } else if (rc == PGPU_OK) {
+    rc = compact_into(qq->ctx, qq->ws, &F, qq->ws->fold.p, qq->ws->stream, out_keys, out_cells, capacity,
+                      out_num_groups, order);
+  }
+  if (rc == PGPU_OK && out_layout) *out_layout = F;
+  pgpu_query_release(qq);
+  return rc;
+}
+
 }  // extern "C"
 
 // ---- per-segment filter planning from literal predicates (pgpu_query_*_expr) --------------------------------------
@@ -4470,7 +4580,9 @@ static int submit_impl(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_t
   }
   // small tables (aggregation only, or up to a few hundred thousand keys) are exported whole into pinned host
   // memory right behind the kernel and compacted on the host: pgpu_query_collect then synchronises once
-  const bool small = bytes <= (8u << 20);
+  // (PGPU_Q_FOLD: the table is folded on the device at collect; neither exported nor compacted as it stands)
+  const bool folded = (q->flags & PGPU_Q_FOLD) != 0;
+  const bool small = !folded && bytes <= (8u << 20);
   void* h_table_dev = nullptr;
   if (small) {
     e = tws->h_table.ensure(bytes);
@@ -4485,7 +4597,7 @@ static int submit_impl(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_t
   // wait in collect() behind query i+1's kernel, which holds every CU (the table stays intact, so a collect with
   // another order still selects from it)
   const bool ordered = order && order->k > 0 && L.num_keys > order->k;
-  rc = launch_impl(ctx, q, ctx->qstream, tws->table.p, tws->table.n, (int64_t*)h_table_dev, &qq, !small,
+  rc = launch_impl(ctx, q, ctx->qstream, tws->table.p, tws->table.n, (int64_t*)h_table_dev, &qq, !small && !folded,
                    ordered ? order : nullptr);
   if (rc) {
     release_ws(ctx, tws);

@@ -288,11 +288,21 @@ def _agg_column(a, result_name: bool) -> Tuple[str, str]:
     return name, {"COUNT": LONG, "COUNTMV": LONG, "AVG": OBJECT, "AVGMV": OBJECT}.get(fn, DOUBLE)
 
 
+def _refuse_distinct(query: QueryContext) -> None:
+    """DISTINCTCOUNT's broker-mergeable intermediate is the value set (DistinctCountAggregationFunction.java:252-310),
+    which the folded table no longer holds: no DataTable for such a query."""
+    if any(a.function == "DISTINCTCOUNT" for a in query.aggregations):
+        from ._lib import PGPU_E_UNSUPPORTED, UnsupportedPlanError
+        raise UnsupportedPlanError(PGPU_E_UNSUPPORTED, "no DataTable for a DISTINCTCOUNT query: its intermediate "
+                                                       "result is the value set")
+
+
 def server_data_table(query: QueryContext, result, group_types: Sequence[int] = ()) -> DataTable:
     """IntermediateResultsBlock.getDataTable of a combined result (QueryResult): the group rows the server's
     IndexedTable returns (group values + intermediate results) or the one aggregation row, with the statistics
     attachMetadataToDataTable puts (numResizes / resizeTimeMs 0: the GPU table never resizes).  `group_types`: the
     group columns' stored types (PGPU_INT ...)."""
+    _refuse_distinct(query)
     aggs = [_agg_column(a, bool(query.group_by)) for a in query.aggregations]
     if query.group_by:
         schema = DataSchema(list(query.group_by) + [n for n, _ in aggs],
@@ -357,6 +367,7 @@ class BrokerResult:
 def reduce_data_tables(query: QueryContext, tables: Sequence[DataTable]) -> BrokerResult:
     """GroupByDataTableReducer / AggregationDataTableReducer over the servers' DataTables."""
     from .plan import order_and_limit, to_select_order
+    _refuse_distinct(query)
     res = BrokerResult(rows=[])
     for t in tables:
         md = t.metadata

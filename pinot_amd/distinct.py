@@ -1,0 +1,187 @@
+"""DISTINCTCOUNT on the GPU path: lowered to GROUP BY queries whose tables are folded on the device, and raised back.
+
+DistinctCountAggregationFunction (core/query/aggregation/function/DistinctCountAggregationFunction.java:66-250) keeps a
+bitmap of the column's dictionary ids per group and turns it into a value set only to merge segments (:252-310); the
+final result is the set's size as an INT (:303-310).  With the sorted global dictionaries of the group-by path, "which
+(group, id) pairs occur" is the occupancy of the table ``GROUP BY g_1..g_n, c`` builds, so a query ``Q`` with
+aggregations ``A + {DISTINCTCOUNT(c)}`` over group columns ``g`` runs as
+
+    Q'  = aggregations A (COUNT(*) when A is empty), GROUP BY g_1..g_n, c      (c last: key = g + inner * cid)
+
+and the partial table of ``Q'`` is folded over ``cid`` on the device (pgpu_query_collect_fold, include/pinot_gpu.h)
+into the table ``GROUP BY g`` alone produces plus one section: the number of occupied ``cid`` per ``g``.
+
+Several DISTINCTCOUNT columns run one pass each, all in flight together like the passes of FILTER clauses; the first
+carries ``A``, the others only COUNT(*); a column named twice is computed once.  The passes share the filter, so they
+meet the same groups and are joined on the group key.
+"""
+from __future__ import annotations
+
+import copy
+import math
+import struct
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
+
+from . import _lib
+from ._lib import UnsupportedPlanError
+from .query import MV_AGGS, AggregationSpec, OrderByExpr, QueryContext
+
+UNLIMITED = 1 << 62
+DISTINCT = "DISTINCTCOUNT"
+
+
+def has_distinct(query: QueryContext) -> bool:
+    return any(a.function == DISTINCT for a in query.aggregations)
+
+
+def _unsupported(why: str) -> UnsupportedPlanError:
+    return UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED, why)
+
+
+@dataclass
+class DistinctPass:
+    """One pass of a DISTINCTCOUNT query."""
+    query: QueryContext     # Q': GROUP BY g..., column with the pass's plain aggregations
+    folded: QueryContext    # what the folded table answers: GROUP BY g... with Q's aggregations + DISTINCTCOUNT(column)
+    column: str             # the folded column
+    plain: List[int]        # original indexes of Q's aggregations, in their order ([]: Q' carries an inserted COUNT(*))
+    distinct: List[int]     # original indexes of DISTINCTCOUNT(column) (every mention of it)
+
+
+def lower(query: QueryContext) -> List[DistinctPass]:
+    """The passes of a DISTINCTCOUNT query.  Raises UnsupportedPlanError for the combinations not served."""
+    if not has_distinct(query):
+        raise ValueError("query has no DISTINCTCOUNT")
+    if query.has_filtered_aggregations:
+        raise _unsupported("DISTINCTCOUNT in a query with FILTER(WHERE ...) aggregations")
+    if any(a.function in MV_AGGS for a in query.aggregations):
+        raise _unsupported("DISTINCTCOUNT together with *MV aggregations")
+    plain = [i for i, a in enumerate(query.aggregations) if a.function != DISTINCT]
+    by_col: Dict[str, List[int]] = {}
+    for i, a in enumerate(query.aggregations):
+        if a.function == DISTINCT:
+            if a.column in query.group_by:
+                raise _unsupported(f"DISTINCTCOUNT of the group column {a.column!r}")
+            by_col.setdefault(a.column, []).append(i)
+    passes = []
+    for k, (col, idx) in enumerate(by_col.items()):
+        mine = plain if k == 0 else []
+        aggs = [query.aggregations[i] for i in mine] or [AggregationSpec("COUNT", None)]
+        groups = list(query.group_by)
+        low = QueryContext(table=query.table, select=groups + [col] + aggs, aggregations=list(aggs),
+                           filter=query.filter, group_by=groups + [col], order_by=[], limit=UNLIMITED,
+                           options=dict(query.options))
+        faggs = list(aggs) + [AggregationSpec(DISTINCT, col)]
+        folded = QueryContext(table=query.table, select=groups + faggs, aggregations=faggs, filter=query.filter,
+                              group_by=groups, order_by=[], limit=UNLIMITED, options=dict(query.options))
+        passes.append(DistinctPass(low, folded, col, list(mine), idx))
+    return passes
+
+
+def order_pass(query: QueryContext, passes: Sequence[DistinctPass]) -> Optional[Tuple[int, OrderByExpr]]:
+    """(pass, expression) the server's ORDER BY trim selects by: the first ORDER BY expression, in the pass whose folded
+    table holds it -- a group column or a plain aggregation in the first pass, DISTINCTCOUNT(c) in c's pass.  The other
+    passes return every group; the join keeps the groups every pass returned."""
+    if not query.group_by or not query.order_by:
+        return None
+    ob = query.order_by[0]
+    for pi, p in enumerate(passes):
+        if ob.expression == f"{DISTINCT.lower()}({p.column})":
+            return pi, ob
+    return 0, ob
+
+
+def _join_stats(query: QueryContext, results: Sequence):
+    """Statistics of the joined passes: the doc counts of one pass (every pass has the same filter),
+    numEntriesScannedPostFilter over the original query's projected columns (they include the distinct columns),
+    kernel time and byte counters summed."""
+    st = copy.copy(results[0].stats)
+    for r in results[1:]:
+        st.kernel_ms += r.stats.kernel_ms
+        st.sparse_sector_bytes += r.stats.sparse_sector_bytes
+        st.dense_bytes += r.stats.dense_bytes
+    st.num_entries_scanned_post_filter = st.num_docs_scanned * len(query.projected_columns)
+    return st
+
+
+def raise_result(query: QueryContext, passes: Sequence[DistinctPass], results: Sequence):
+    """The original query's QueryResult from the passes' folded results (QueryResults of ``DistinctPass.folded``)."""
+    from .plan import QueryResult, order_and_limit, to_select_order
+
+    res = QueryResult(query=query, stats=_join_stats(query, results))
+    na = len(query.aggregations)
+
+    def place(fin: list, p: DistinctPass, vals: Sequence) -> None:
+        for j, i in enumerate(p.plain):
+            fin[i] = vals[j]
+        for i in p.distinct:
+            fin[i] = int(vals[-1])  # ColumnDataType.INT (DistinctCountAggregationFunction.java:303-310)
+
+    if not query.group_by:
+        fin: list = [None] * na
+        for p, r in zip(passes, results):
+            place(fin, p, r.aggregation_result)
+        res.aggregation_result = fin
+        res.rows = [to_select_order(query, tuple(fin))]
+        return res
+    ng = len(query.group_by)
+    others = [{tuple(r[:ng]): r[ng:] for r in rr.group_rows} for rr in results[1:]]
+    rows = []
+    for r in results[0].group_rows:
+        key = tuple(r[:ng])
+        if not all(key in m for m in others):
+            continue  # trimmed away by the pass that carries the ORDER BY expression
+        fin = [None] * na
+        place(fin, passes[0], r[ng:])
+        for p, m in zip(passes[1:], others):
+            place(fin, p, m[key])
+        rows.append(key + tuple(fin))
+    res._group_rows = rows
+    res.rows = [to_select_order(query, r) for r in order_and_limit(query, rows)]
+    return res
+
+
+def value_key(v):
+    """Identity of a column value in a distinct set: FLOAT / DOUBLE by their bits (one NaN), as the group keys."""
+    if isinstance(v, float):
+        return ("f", "nan" if math.isnan(v) else struct.pack(">d", v))
+    return v
+
+
+def value_keys(values) -> set:
+    """value_key of every entry of a dictionary (numpy array or list of strings) or list of group values."""
+    vals = values.tolist() if hasattr(values, "tolist") else list(values)
+    return {value_key(v) for v in vals}
+
+
+def unfolded_result(query: QueryContext, passes: Sequence[DistinctPass], results: Sequence):
+    """The scanned half of a partly non-scan aggregation-only query, from the passes' *unfolded* results (QueryResults
+    of ``DistinctPass.query``, one group per value of the distinct column): (QueryResult with the plain aggregations
+    merged over the groups, {original aggregation index: the value set as value_key}).  Only COUNT / MIN / MAX occur
+    beside DISTINCTCOUNT in a non-scan plan (AggregationPlanNode.java:185-197)."""
+    from .plan import QueryResult
+
+    na = len(query.aggregations)
+    fin: list = [None] * na
+    sets: Dict[int, set] = {}
+    for p, r in zip(passes, results):
+        rows = r.group_rows
+        for j, i in enumerate(p.plain):
+            fn = query.aggregations[i].function
+            col = [row[1 + j] for row in rows]
+            if fn == "COUNT":
+                fin[i] = int(sum(col))
+            elif fn == "MIN":
+                fin[i] = min(col, default=math.inf)
+            elif fn == "MAX":
+                fin[i] = max(col, default=-math.inf)
+            else:
+                raise _unsupported(f"{fn} beside DISTINCTCOUNT in a non-scan plan")
+        keys = value_keys([row[0] for row in rows])
+        for i in p.distinct:
+            sets[i] = keys
+            fin[i] = len(keys)
+    res = QueryResult(query=query, stats=_join_stats(query, results))
+    res.aggregation_result = fin
+    return res, sets

@@ -61,6 +61,7 @@ class GpuNode:
 
     def execute(self, query: QueryContext, segments_by_device: Sequence[Sequence[GpuSegment]]) -> QueryResult:
         """One query over every device's segments, merged inside the library."""
+        _refuse_distinct(query)
         if has_mv_aggregations(query):  # *MV aggregations over row columns (pinot_amd/mv.py)
             check_group_columns(query, [s for segs in segments_by_device for s in segs])
             low, parts = mv_lower(query)
@@ -70,6 +71,7 @@ class GpuNode:
     def submit(self, query: QueryContext, segments_by_device: Sequence[Sequence[GpuSegment]]) -> "_NodePending":
         """Plan the query for every device and launch them (pgpu_node_submit); several may be in flight, collected
         in submission order."""
+        _refuse_distinct(query)
         if len(segments_by_device) != len(self.contexts):
             raise ValueError("one segment list per device")
         everything = [s for segs in segments_by_device for s in segs]
@@ -150,6 +152,14 @@ class GpuNode:
                                dense_bytes=st.dense_bytes, filter_stats_exact=bool(st.filter_stats_exact),
                                kernel_variant=st.kernel_variant)
         return finish(query, GroupTable.sorted(k, c, L), globs, stats)
+
+
+def _refuse_distinct(query: QueryContext) -> None:
+    """DISTINCTCOUNT on a node needs the fold after the devices' tables are merged (pgpu_table_fold on the merged
+    table), which pgpu_node_collect does not do yet: the server keeps its CPU plan."""
+    if any(a.function == "DISTINCTCOUNT" for a in query.aggregations):
+        raise _lib.UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED,
+                                        "DISTINCTCOUNT is not served by the node-level combine (GpuNode)")
 
 
 class _NodePending:

@@ -47,6 +47,7 @@ from .segment import DOCID_COLUMN, GpuContext, GpuSegment
 AGG_FN = {"COUNT": PGPU_AGG_COUNT, "SUM": PGPU_AGG_SUM, "MIN": PGPU_AGG_MIN, "MAX": PGPU_AGG_MAX,
           "AVG": PGPU_AGG_AVG}
 DEFAULT_NUM_GROUPS_LIMIT = 100_000          # InstancePlanMakerImplV2.java:73-74
+LOWERED_ROWS, LOWERED_FOLD = 1, 2           # GpuPlanMaker._prepare: how a lowered DISTINCTCOUNT pass is collected
 DEFAULT_MAX_INIT_GROUP_HOLDER_CAPACITY = 10_000
 
 
@@ -340,6 +341,9 @@ class QueryResult:
     @property
     def intermediate(self) -> Optional[dict]:
         """group values -> intermediate values (AVG as (sum, count))."""
+        if any(a.function == "DISTINCTCOUNT" for a in self.query.aggregations):
+            # the broker-mergeable form of DISTINCTCOUNT is the value set, which the folded table no longer holds
+            raise UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED, "no intermediate result for a DISTINCTCOUNT query")
         if self._intermediate is None and self._columns is not None:
             self._intermediate = self._columns.intermediate()
         return self._intermediate
@@ -384,6 +388,8 @@ def final_value(fn: str, cell_count: int, cell: Optional[int], op: int, vtype: i
     """AggregationFunction.extractFinalResult on a merged cell (an exact Python int for integer sums)."""
     if fn == "COUNT":
         return int(cell_count)
+    if fn == "DISTINCTCOUNT":  # the appended section of a folded table (pgpu_fold_layout_of)
+        return int(cell)
     if fn == "SUM":
         return float(cell) if op == PGPU_RED_SUM_I64 else float(np.int64(cell).view(np.float64))
     if fn in ("MIN", "MAX"):
@@ -442,7 +448,9 @@ def topk_spec(query: QueryContext, cards: Sequence[int], k: int, key_base: int =
         t._keep = carr  # the cardinalities live as long as the spec
     else:
         t.source, t.agg_index = _lib.PGPU_TOPK_AGG, i - ng
-        t.agg_fn = AGG_FN[query.aggregations[i - ng].function]
+        fn = query.aggregations[i - ng].function
+        # (a folded table's distinct count is a LONG SUM section: pgpu_fold_layout_of)
+        t.agg_fn = PGPU_AGG_SUM if fn == "DISTINCTCOUNT" else AGG_FN[fn]
     return t
 
 
@@ -530,6 +538,7 @@ class GpuPlanMaker:
         # (a dashboard's repeated query) reuses its filter program, descriptor and trim -- only the deadline is
         # restamped.  Dropped whenever a global dictionary or a segment it names changes.
         self._prepared: Dict[tuple, tuple] = {}
+        self._distinct: Dict[int, tuple] = {}  # id(query) -> (query, its DISTINCTCOUNT passes)
         if hasattr(ctx, "add_listener"):
             ctx.add_listener(self)  # segment_released: forget global dictionaries naming a released segment
 
@@ -682,12 +691,14 @@ class GpuPlanMaker:
 
     def build_desc(self, query: QueryContext, segments: Sequence[GpuSegment], plan_filters: bool = True,
                    extra_flags: int = 0, reduce_docs: int = 0,
-                   sum_layout: Optional[Tuple[Sequence[int], Sequence[int]]] = None):
+                   sum_layout: Optional[Tuple[Sequence[int], Sequence[int]]] = None,
+                   num_groups_limit: Optional[int] = None):
         """Build the pgpu_query_desc.  Returns (desc, keep, globals_): `keep` owns every buffer the descriptor
         points to (one node array, one id pool, one column-map array, one remap-handle array, one plan array).
         plan_filters=False leaves the per-segment filter programs empty (the library plans them from
         filter_expr); sum_layout = (exps, parts) per aggregation is the floating SUMs' fixed-point layout that callers
-        combining tables across ranks agree on (fixed_window; pgpu_query_desc.sum_exp / sum_parts)."""
+        combining tables across ranks agree on (fixed_window; pgpu_query_desc.sum_exp / sum_parts);
+        num_groups_limit overrides the maker's (a lowered DISTINCTCOUNT pass runs with none)."""
         columns = list(query.columns)
         col_index = {c: i for i, c in enumerate(columns)}
         nseg = len(segments)
@@ -771,7 +782,8 @@ class GpuPlanMaker:
                          group_columns=gcols, group_cardinalities=gcards,
                          flags=(_lib.PGPU_Q_STATS if self.collect_stats else 0) | self.query_flags | extra_flags |
                          (_lib.PGPU_Q_EXACT_FILTER_STATS if self.exact_filter_stats else 0),
-                         reduce_docs=reduce_docs, num_groups_limit=self.num_groups_limit,
+                         reduce_docs=reduce_docs,
+                         num_groups_limit=self.num_groups_limit if num_groups_limit is None else num_groups_limit,
                          # NoDictionary*GroupKeyGenerator caps every key space at numGroupsLimit: with a raw group
                          # column no segment is array-based (a segment meeting more keys goes back to the CPU)
                          array_based_threshold=0 if no_dict else self.max_init_group_holder_capacity,
@@ -789,6 +801,8 @@ class GpuPlanMaker:
         """Plan the query and enqueue it on the GPU without waiting (pgpu_query_submit).  Several queries may be
         in flight: the host plans the next one while the GPU runs this one.  *MV aggregations run lowered onto
         the multi-value columns' row columns (pinot_amd/mv.py) and are raised back in collect()."""
+        if has_distinct(query):
+            return self.submit_distinct(query, segments)
         if has_mv_aggregations(query):
             check_group_columns(query, segments)
             low, parts = mv_lower(query)
@@ -798,23 +812,38 @@ class GpuPlanMaker:
         if query.has_filtered_aggregations:
             raise _lib.UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED,
                                             "filtered aggregations run one pass per FILTER clause: use execute()")
+        return self._launch(self._prepare(query, segments), segments)
+
+    def _prepare(self, query: QueryContext, segments: Sequence[GpuSegment], lowered: int = 0) -> tuple:
+        """The filter program, descriptor, layout and trim of a query over these segments, from the prepared cache
+        when the same query object was submitted before.  lowered: a pass of a DISTINCTCOUNT query (distinct_lower)
+        -- no numGroupsLimit (the limit holds the group keys, not the distinct set; check_distinct has checked
+        them) and no trim (its order refers to the folded table); LOWERED_FOLD: collected through
+        pgpu_query_collect_fold (PGPU_Q_FOLD), LOWERED_ROWS: through the plain collect.  Such a pass has a cache
+        key of its own kind."""
         pkey = (id(query), tuple(s.uid for s in segments), self.collect_stats, self.exact_filter_stats,
                 self.query_flags, self.num_groups_limit, self.max_init_group_holder_capacity, self.host_planning,
-                self.gpu_topk, self.min_server_group_trim_size)
+                self.gpu_topk, self.min_server_group_trim_size, lowered)
         hit = self._prepared.get(pkey)
         if hit is not None and hit[0] is query:
-            _, expr, desc, keep, globals_, L, order = hit
+            desc = hit[2]
             desc.deadline_ms = 0 if self.timeout_ms is None else int(time.time() * 1000) + int(self.timeout_ms)
-        else:
-            expr = self.filter_expr(query, segments)
-            desc, keep, globals_ = self.build_desc(query, segments, plan_filters=expr is None)
-            L = self.layout(desc)
-            # the server trim is known now: big tables are ranked and compacted behind the kernels (collect only
-            # copies)
-            order = self.trim_order(query, globals_)
-            if len(self._prepared) >= 32:
-                self._prepared.clear()
-            self._prepared[pkey] = (query, expr, desc, keep, globals_, L, order)
+            return hit
+        expr = self.filter_expr(query, segments)
+        desc, keep, globals_ = self.build_desc(query, segments, plan_filters=expr is None,
+                                               extra_flags=_lib.PGPU_Q_FOLD if lowered == LOWERED_FOLD else 0,
+                                               num_groups_limit=0 if lowered else None)
+        L = self.layout(desc)
+        # the server trim is known now: big tables are ranked and compacted behind the kernels (collect only
+        # copies)
+        order = None if lowered else self.trim_order(query, globals_)
+        if len(self._prepared) >= 32:
+            self._prepared.clear()
+        hit = self._prepared[pkey] = (query, expr, desc, keep, globals_, L, order)
+        return hit
+
+    def _launch(self, prepared: tuple, segments: Sequence[GpuSegment]) -> "PendingQuery":
+        query, expr, desc, keep, globals_, L, order = prepared
         h = C.c_void_p()
         _lib.check(self.ctx._lib.pgpu_query_submit_ordered(
             self.ctx.handle, C.byref(desc), expr[0] if expr is not None else None, expr[1] if expr is not None else 0,
@@ -826,6 +855,116 @@ class GpuPlanMaker:
                                                              len(segments)))
         return pq
 
+    # -- DISTINCTCOUNT (pinot_amd/distinct.py) --
+    def distinct_passes(self, query: QueryContext) -> list:
+        """distinct_lower(query), kept per query object so that a re-submitted query meets its prepared passes."""
+        hit = self._distinct.get(id(query))
+        if hit is not None and hit[0] is query:
+            return hit[1]
+        passes = distinct_lower(query)
+        if len(self._distinct) >= 32:
+            self._distinct.clear()
+        self._distinct[id(query)] = (query, passes)
+        return passes
+
+    def check_distinct(self, query: QueryContext, passes, segments: Sequence[GpuSegment]) -> None:
+        """What a DISTINCTCOUNT query needs of its segments, checked before anything is launched: single-value
+        distinct columns, and group keys that cannot reach numGroupsLimit in any segment -- the reference's holder
+        limit applies to the group keys only (the distinct sets are unbounded), so the lowered passes run without a
+        limit, and neither the first-seen cut nor numGroupsLimitReached may then be possible."""
+        check_group_columns(query, segments)
+        for p in passes:
+            if segments and segments[0].column(p.column).is_mv:
+                raise UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED,
+                                           f"DISTINCTCOUNT over the multi-value column {p.column!r}")
+        if query.group_by and self.num_groups_limit > 0:
+            for s in segments:
+                space = 1
+                for g in query.group_by:
+                    space *= max(1, s.column(s.group_view(g)).cardinality)
+                if space >= self.num_groups_limit:
+                    raise UnsupportedPlanError(
+                        _lib.PGPU_E_UNSUPPORTED,
+                        f"DISTINCTCOUNT with a group key space of {space} in segment {s.name!r}: not below "
+                        f"numGroupsLimit {self.num_groups_limit}")
+
+    def submit_distinct(self, query: QueryContext, segments: Sequence[GpuSegment]) -> "DistinctPending":
+        """Submit every pass of a DISTINCTCOUNT query (all in flight together).  Everything that can refuse the
+        query -- unsupported combinations, numGroupsLimit, a table the fold does not take -- does so before the
+        first launch."""
+        passes = self.distinct_passes(query)
+        # (kept with the prepared submissions, and dropped with them: what was checked and laid out once)
+        rkey = ("distinct", id(query), tuple(s.uid for s in segments), self.collect_stats, self.exact_filter_stats,
+                self.query_flags, self.num_groups_limit, self.max_init_group_holder_capacity, self.host_planning,
+                self.gpu_topk, self.min_server_group_trim_size)
+        hit = self._prepared.get(rkey)
+        if hit is not None and hit[0] is query:
+            ready = hit[1]
+            for prep, _, _, _ in ready:
+                self._prepare(prep[0], segments, lowered=LOWERED_FOLD)  # (restamps the deadline)
+        else:
+            ready = self._ready_distinct(query, passes, segments)
+            self._prepared[rkey] = (query, ready)
+        pending = []
+        for p, (prep, inner, F, order) in zip(passes, ready):
+            pq = self._launch(prep, segments)
+            pq.fold = (inner, F, p.folded)
+            pq.order = order
+            pending.append(pq)
+        return DistinctPending(self, query, passes, pending)
+
+    def _ready_distinct(self, query: QueryContext, passes, segments: Sequence[GpuSegment]) -> list:
+        """Per pass: (prepared submission, inner keys, folded layout, trim order over the folded table)."""
+        self.check_distinct(query, passes, segments)
+        op = order_pass(query, passes) if self.gpu_topk and self.min_server_group_trim_size > 0 else None
+        ready = []
+        for pi, p in enumerate(passes):
+            prep = self._prepare(p.query, segments, lowered=LOWERED_FOLD)
+            globals_, L = prep[4], prep[5]
+            inner = 1
+            for g in globals_[:-1]:
+                inner *= len(g[0])
+            F = TableLayout()
+            _lib.check(self.ctx._lib.pgpu_fold_layout_of(C.byref(L), inner, C.byref(F)))
+            order = None
+            if op is not None and op[0] == pi:
+                # the trim's order over the folded table: its aggregation entries are Q's, then the distinct count
+                order = topk_spec(dataclasses.replace(p.folded, order_by=[op[1]]), [len(g[0]) for g in globals_[:-1]],
+                                  table_capacity(query.limit, self.min_server_group_trim_size))
+            ready.append((prep, inner, F, order))
+        return ready
+
+    def collect_distinct(self, pending: "DistinctPending") -> QueryResult:
+        """Collect every pass (also after one failed: each owns a query handle) and join them."""
+        results, err = [], None
+        for pq in pending.pending:
+            try:
+                results.append(self.collect(pq))
+            except _lib.PinotGpuError as e:
+                err = err or e
+        pending.pending = []
+        if err is not None:
+            raise err
+        return distinct_raise(pending.query, pending.passes, results)
+
+    def execute_distinct(self, query: QueryContext, segments: Sequence[GpuSegment]) -> QueryResult:
+        passes = self.distinct_passes(query)
+        non_scan = self.non_scan_segments(query, segments)
+        if not any(non_scan):
+            return self.collect_distinct(self.submit_distinct(query, segments))
+        # NonScanBasedAggregationOperator answers DISTINCTCOUNT from the dictionary (AggregationPlanNode.java:185-197):
+        # the scanned segments' tables come back unfolded -- their rows are the value sets -- and are united on the
+        # host with the non-scan segments' dictionaries
+        rest = [s for s, ns in zip(segments, non_scan) if not ns]
+        meta = [s for s, ns in zip(segments, non_scan) if ns]
+        if not rest:
+            return merge_non_scan(query, None, meta)
+        self.check_distinct(query, passes, rest)
+        pending = [self._launch(self._prepare(p.query, rest, lowered=LOWERED_ROWS), rest) for p in passes]
+        from .distinct import unfolded_result
+        scanned, sets = unfolded_result(query, passes, [self.collect(pq) for pq in pending])
+        return merge_non_scan(query, scanned, meta, sets)
+
     def trim_order(self, query: QueryContext, globals_) -> Optional[_lib.TopK]:
         """The IndexedTable trim of GROUP BY ... ORDER BY ... LIMIT (table_capacity(limit), ties kept) as a
         pgpu_topk, or None when every group comes back (no ORDER BY, trim disabled, or gpu_topk off)."""
@@ -836,11 +975,16 @@ class GpuPlanMaker:
 
     def collect(self, pending: "PendingQuery") -> QueryResult:
         """Wait for a submitted query and finish it (pgpu_query_collect + ORDER BY / LIMIT on the host)."""
+        if isinstance(pending, DistinctPending):
+            return self.collect_distinct(pending)
         if pending.mv is not None:
             query, parts = pending.mv
             pending.mv = None
             return mv_raise(query, parts, self.collect(pending))
         L = pending.layout
+        fold = pending.fold
+        if fold is not None:  # a DISTINCTCOUNT pass: the rows of its table folded over the distinct column
+            L = fold[1]
         cap = int(min(L.num_keys, 1 << 26))
         kw = key_words_out(L)
         keys = np.empty(max(cap, 1) * kw, dtype=np.int64)
@@ -850,10 +994,17 @@ class GpuPlanMaker:
         h, pending.handle = pending.handle, None
         query = pending.query
         order = pending.order
-        _lib.check(self.ctx._lib.pgpu_query_collect_topk(h, C.byref(order) if order is not None else None,
-                                                         keys.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                         cells.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(n),
-                                                         C.byref(st)))
+        if fold is not None:
+            query = fold[2]
+            _lib.check(self.ctx._lib.pgpu_query_collect_fold(h, fold[0], C.byref(order) if order is not None else None,
+                                                             keys.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                             cells.ctypes.data_as(C.POINTER(C.c_int64)), cap,
+                                                             C.byref(n), C.byref(st), None))
+        else:
+            _lib.check(self.ctx._lib.pgpu_query_collect_topk(h, C.byref(order) if order is not None else None,
+                                                             keys.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                             cells.ctypes.data_as(C.POINTER(C.c_int64)), cap,
+                                                             C.byref(n), C.byref(st)))
         table = GroupTable.sorted(keys[: n.value * kw].reshape(-1, kw) if kw > 1 else keys[: n.value],
                                   cells[: n.value], L)
         stats = ExecutionStats(num_docs_scanned=st.num_docs_scanned,
@@ -866,9 +1017,12 @@ class GpuPlanMaker:
                                num_segments_matched=st.num_segments_matched,
                                segment_matched=pending.matched[:pending.num_segments].copy(),
                                kernel_variant=st.kernel_variant)
-        return finish(query, table, [g[0] for g in pending.globals_], stats)
+        gdicts = [g[0] for g in pending.globals_]
+        return finish(query, table, gdicts[:-1] if fold is not None else gdicts, stats)
 
     def execute(self, query: QueryContext, segments: Sequence[GpuSegment]) -> QueryResult:
+        if has_distinct(query):
+            return self.execute_distinct(query, segments)
         if query.has_filtered_aggregations:
             parts = split_filtered_aggregations(query)
             pending = [self.submit(sq, segments) for sq, _ in parts]  # all in flight, then collected in order
@@ -955,12 +1109,20 @@ class GpuPlanMaker:
         :171-195): a filter that folds to match-all plus only COUNT / MIN / MAX is answered from segment metadata
         and the dictionary, with no scan (NonScanBasedAggregationOperator)."""
         q = query
-        if q.group_by or q.has_filtered_aggregations or any(a.function not in ("COUNT", "MIN", "MAX", "MINMV", "MAXMV")
-                                                            for a in q.aggregations):
+        fns = ("COUNT", "MIN", "MAX", "MINMV", "MAXMV", "DISTINCTCOUNT")
+        if q.group_by or q.has_filtered_aggregations or any(a.function not in fns for a in q.aggregations):
             return [False] * len(segments)
+
+        def answers(s: GpuSegment, a: AggregationSpec) -> bool:
+            if a.function == "COUNT":
+                return True
+            if a.function == "DISTINCTCOUNT":  # the dictionary's size: dictionary-encoded single-value columns only
+                col = s.column(a.column)
+                return not col.is_raw and not col.is_mv and s.dictionaries.get(a.column) is not None
+            return s.min_max(a.column) is not None
+
         return [s.num_docs > 0 and SegmentFilterPlanner(s).build(q.filter).kind == "ALL" and
-                all(s.min_max(a.column) is not None for a in q.aggregations if a.function != "COUNT")
-                for s in segments]
+                all(answers(s, a) for a in q.aggregations) for s in segments]
 
 
 @dataclass
@@ -975,6 +1137,7 @@ class PendingQuery:
     mv: Optional[tuple] = None  # (original query, lowered aggregation indexes) when *MV aggregations were lowered
     matched: Optional[np.ndarray] = None  # per-segment matched flags, filled by the wait (pgpu_query_matched_segments)
     order: Optional[object] = None  # the pgpu_topk given at submit (collect passes the same one)
+    fold: Optional[tuple] = None  # a DISTINCTCOUNT pass: (inner keys, folded layout, folded query) for collect
 
     def cancel(self) -> None:
         """Stop the query (pgpu_query_cancel): its kernels skip their remaining tiles and collect raises
@@ -1065,13 +1228,23 @@ def finish(query: QueryContext, table: GroupTable, global_dicts: Sequence, stats
     return res
 
 
-def merge_non_scan(query: QueryContext, scanned: Optional[QueryResult], segments: Sequence[GpuSegment]) -> QueryResult:
+def merge_non_scan(query: QueryContext, scanned: Optional[QueryResult], segments: Sequence[GpuSegment],
+                   value_sets: Optional[Dict[int, set]] = None) -> QueryResult:
     """Merge the scanned segments' result with the non-scan segments' metadata answers
-    (NonScanBasedAggregationOperator.java:85-101: COUNT = total docs, MIN / MAX = dictionary min / max as double;
-    statistics (numTotalDocs, 0, 0, numTotalDocs) per segment, :253-256)."""
+    (NonScanBasedAggregationOperator.java:85-101: COUNT = total docs, MIN / MAX = dictionary min / max as double,
+    DISTINCTCOUNT = the dictionary's values; statistics (numTotalDocs, 0, 0, numTotalDocs) per segment, :253-256).
+    value_sets: per DISTINCTCOUNT aggregation the scanned segments' value set (distinct.unfolded_result), united here
+    with the non-scan segments' dictionaries."""
+    from .distinct import value_keys
     res = QueryResult(query=query, stats=ExecutionStats() if scanned is None else scanned.stats)
     vals = []
     for ai, a in enumerate(query.aggregations):
+        if a.function == "DISTINCTCOUNT":
+            keys = set(value_sets.get(ai, ())) if value_sets else set()
+            for s in segments:
+                keys |= value_keys(s.dictionaries[a.column])
+            vals.append(len(keys))
+            continue
         v = {"COUNT": 0, "MIN": math.inf, "MAX": -math.inf, "MINMV": math.inf, "MAXMV": -math.inf}[a.function] \
             if scanned is None else scanned.aggregation_result[ai]
         for s in segments:
@@ -1186,6 +1359,8 @@ class GroupColumns:
         s = None
         if fn == "COUNT":
             f = cnt.astype(np.int64)
+        elif fn == "DISTINCTCOUNT":
+            f = cell.astype(np.int64)
         elif fn in ("SUM", "AVG") and L.agg_sum_parts[ai] > 1:
             # split sum: join the parts exactly (Python ints), round once to double (fixed point: times 2^exp)
             e, parts = sum_exp_of(L, ai), L.agg_sum_parts[ai]
@@ -1245,7 +1420,7 @@ class GroupColumns:
         parts = [self.value(gi, idx).tolist() for gi in range(len(self.global_dicts))]
         for ai, a in enumerate(self.query.aggregations):
             f = self.final(ai, idx)[0]
-            parts.append([int(x) for x in f.tolist()] if a.function == "COUNT" else f.tolist())
+            parts.append([int(x) for x in f.tolist()] if a.function in ("COUNT", "DISTINCTCOUNT") else f.tolist())
         return [tuple(r) for r in zip(*parts)] if parts else []
 
     def intermediate(self) -> dict:
@@ -1278,3 +1453,38 @@ def mv_lower(query: QueryContext):
 def mv_raise(query: QueryContext, parts, low_res):
     from .mv import raise_result
     return raise_result(query, parts, low_res)
+
+
+def has_distinct(query: QueryContext) -> bool:
+    return any(a.function == "DISTINCTCOUNT" for a in query.aggregations)
+
+
+def distinct_lower(query: QueryContext):
+    """The passes of a DISTINCTCOUNT query (pinot_amd/distinct.py): each a lowered QueryContext (GROUP BY g..., c),
+    the folded column, and the indexes of the original aggregations it answers."""
+    from .distinct import lower
+    return lower(query)
+
+
+def distinct_raise(query: QueryContext, passes, results):
+    """The original query's result from the passes' folded results, joined on the group key."""
+    from .distinct import raise_result
+    return raise_result(query, passes, results)
+
+
+def order_pass(query: QueryContext, passes):
+    from .distinct import order_pass as f
+    return f(query, passes)
+
+
+@dataclass
+class DistinctPending:
+    """A submitted, not yet collected DISTINCTCOUNT query: one PendingQuery per pass."""
+    maker: "GpuPlanMaker"
+    query: QueryContext
+    passes: list
+    pending: List[PendingQuery]
+
+    def cancel(self) -> None:
+        for pq in self.pending:
+            pq.cancel()

@@ -46,7 +46,7 @@ class FilterContext:
 
 @dataclass(frozen=True)
 class AggregationSpec:
-    function: str        # COUNT, SUM, MIN, MAX, AVG; COUNTMV, SUMMV, MINMV, MAXMV, AVGMV (multi-value columns)
+    function: str        # COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT; COUNTMV, SUMMV, MINMV, MAXMV, AVGMV (multi-value columns)
     column: Optional[str]  # None for COUNT(*)
     filter_key: Optional[str] = None  # FILTER(WHERE ...) clause text; its FilterContext is QueryContext.agg_filters
 
@@ -118,7 +118,7 @@ class QueryContext:
 # ---- SQL front end -------------------------------------------------------------------------------------------
 _TOKEN = re.compile(r"\s*(?:(?P<num>-?\d+(?:\.\d+)?(?:[eE][-+]?\d+)?)|(?P<str>'(?:[^']|'')*')|"
                     r"(?P<op><>|!=|<=|>=|=|<|>|\(|\)|,|\*)|(?P<id>[A-Za-z_][A-Za-z0-9_.$]*))")
-_AGGS = {"COUNT", "SUM", "MIN", "MAX", "AVG", "COUNTMV", "SUMMV", "MINMV", "MAXMV", "AVGMV"}
+_AGGS = {"COUNT", "SUM", "MIN", "MAX", "AVG", "DISTINCTCOUNT", "COUNTMV", "SUMMV", "MINMV", "MAXMV", "AVGMV"}
 MV_AGGS = {"COUNTMV": "COUNT", "SUMMV": "SUM", "MINMV": "MIN", "MAXMV": "MAX", "AVGMV": "AVG"}
 
 
@@ -189,6 +189,8 @@ class _Parser:
     # select item: agg(col|*) | column
     def select_item(self):
         t, t2 = self.peek(), self.peek(1)
+        if t[0] == "id" and t[1].upper() == "DISTINCTCOUNTMV" and t2 == ("op", "("):
+            raise SqlError("DISTINCTCOUNTMV is not supported (DISTINCTCOUNT over single-value columns only)")
         if t[0] == "id" and t[1].upper() in _AGGS and t2 == ("op", "("):
             fn = t[1].upper()
             self.i += 2
@@ -200,6 +202,9 @@ class _Parser:
             if fn != "COUNT" and col is None:
                 raise SqlError(f"{fn}(*) is not supported")
             key = None
+            nxt = self.peek()
+            if fn == "DISTINCTCOUNT" and nxt[0] == "id" and nxt[1].upper() == "FILTER":
+                raise SqlError("DISTINCTCOUNT with FILTER(WHERE ...) is not supported")
             if self.kw("FILTER"):  # AGG(col) FILTER(WHERE <filter>)
                 self.expect_op("(")
                 self.expect_kw("WHERE")
