@@ -346,6 +346,12 @@ typedef struct {
  * device as it is -- no copy of a small table to the host, no compaction behind the kernels -- since only its fold
  * comes back.  pgpu_query_collect(_topk) still works on such a query (compacting at collect). */
 #define PGPU_Q_FOLD 64ull
+/* pgpu_query_submit* runs a register-direct query with a small table as ONE launch: the query kernel's last
+ * workgroup also does the epilogue (statistics, matched-segment flags, export of the table), the metadata arena is
+ * only copied when its bytes changed and the table's identities were written by the workspace's previous query.
+ * This flag forces the three launches (prologue, query kernel, finalize) instead; results are bit-identical
+ * (tests and tuning; PGPU_SPLIT_LAUNCH=1 in the environment does the same for every query). */
+#define PGPU_Q_SPLIT_LAUNCH 128ull
 
 /* ---- partial-result table ----------------------------------------------------------------------------------
  * A query produces a dense table over G = prod(group_cardinalities) keys (G = 1 for aggregation only), laid out

@@ -38,6 +38,7 @@ PGPU_RED_SUM_I64, PGPU_RED_SUM_F64, PGPU_RED_MIN_I64, PGPU_RED_MAX_I64 = range(4
 PGPU_Q_STATS, PGPU_Q_PARTITION, PGPU_Q_PART_SPILL, PGPU_Q_SUM_SPLIT, PGPU_Q_HASH = 1, 2, 4, 8, 16
 PGPU_Q_EXACT_FILTER_STATS = 32
 PGPU_Q_FOLD = 64  # the table comes back through pgpu_query_collect_fold only
+PGPU_Q_SPLIT_LAUNCH = 128  # prologue / query kernel / finalize as three launches (default: one fused launch)
 PGPU_KEYS_DENSE, PGPU_KEYS_HASH = 0, 1
 PGPU_PART_BITS = 21  # split integer SUM: three sections of 21-bit parts (include/pinot_gpu.h)
 PGPU_SUM_EXP_F64 = 32767  # pgpu_table_layout.agg_sum_exp of a float64 SUM section

@@ -438,6 +438,18 @@ struct DevParams {
   const uint32_t* cand_ct;        // query_kernel_cand: per unit {segment, its container's index in InvLeafX::ct
                                   // (~0u: a sorted leaf's doc range), first doc, last doc}
   uint32_t* fsm_fn;               // query_kernel_rfsm (direct == 8): per-tile transducer maps for andfsm_segment_kernel
+  // Fused launch (query_kernel_rdirect of a submitted query with a small table): every workgroup takes a ticket
+  // after its epilogue and the one that draws gridDim.x - 1 does finalize_kernel's work (fused_finalize), then
+  // writes the identities of this layout into the workspace's spare table for the next query.  fuse == 0: the
+  // kernel ends after its epilogue and finalize_kernel follows as a launch of its own.
+  int32_t fuse;
+  int32_t fuse_nslabs;           // per-wave rows of stats / slab (finalize_kernel's nslabs)
+  uint32_t* fuse_ticket;          // zero between queries (the last workgroup resets it)
+  int64_t* fuse_stats_out;        // pinned host: [PGPU_NSTATS]
+  uint8_t* fuse_seg_out;          // pinned host: [nseg] matched-segment flags
+  int64_t* fuse_host_table;       // pinned host copy of the table (AGG: its cells), or null
+  uint64_t fuse_table_words;      // non-AGG: words of `table` exported to fuse_host_table
+  int64_t* fuse_spare;            // [nsec][G] written with the sections' identities, or null
   uint64_t gstride64[PGPU_MAX_GCOLS];  // HASH: mixed-radix stride of group column g within its key word
   DevAgg aggs[PGPU_MAX_AGGS];
   int32_t gcols[PGPU_MAX_GCOLS];
@@ -445,6 +457,11 @@ struct DevParams {
   int32_t sec_op[PGPU_MAX_SECTIONS];
 };
 static_assert(sizeof(DevParams) <= 4096, "DevParams is a kernel argument");
+
+// Fused launch: dynamic LDS its epilogue uses (fused_finalize), and the largest table (8-byte words) one workgroup
+// exports and re-initialises without outlasting the launches it replaces
+#define PGPU_FUSE_LDS_BYTES 2064
+#define PGPU_FUSE_MAX_TABLE_WORDS 8192
 
 #define PGPU_FLAG_STATS 1
 #define PGPU_FLAG_PROFILE 2   // per-wave phase cycle counters into DevParams::prof (PGPU_PROFILE=1)

@@ -34,6 +34,7 @@
 //   DictionaryBasedGroupKeyGenerator (raw key = mixed radix)      core/query/aggregation/groupby/DictionaryBasedGroupKeyGenerator.java:275-322
 //   AggregationOnlyCombineOperator / GroupByOrderByCombineOperator core/operator/combine/*.java (partials merged in HBM)
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -992,8 +993,17 @@ struct SegState {
 // numSegmentsMatched (CombineOperatorUtils.java:64-67: a segment counts when its numDocsScanned > 0): a plain store of
 // 1 by lane 0 of any wave that matched docs of the segment (same value from every writer, no atomic needed).  `any`
 // must be wave-uniform.
+// What a workgroup hands to the last workgroup of a fused launch (fused_finalize) is stored write-through (an
+// agent-scope store), so that the hand-off needs no release fence, only the drained stores and the ticket: an
+// agent-scope release fence in each of the 1,024 workgroups (an L2 write-back each) measured +26 us on config 5's
+// kernel.  Any other launch: the plain store.
+template <typename T>
+FI void pub_store(const DevParams& p, T* dst, T v) {
+  if (p.fuse) __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else *dst = v;
+}
 FI void mark_seg(const DevParams& p, const SegState& ss, bool any) {
-  if (any && lane_id() == 0) p.segany[ss.sg - p.segs] = 1u;
+  if (any && lane_id() == 0) pub_store(p, &p.segany[ss.sg - p.segs], 1u);
 }
 FI void load_seg(const DevParams& p, int seg, SegState& ss) {
   const DevSeg* sg = p.segs + seg;
@@ -2589,18 +2599,18 @@ FI void direct_epilogue(const DevParams& p, const Lds& L, const Stats& st, int w
 #endif
   if (lane == 0) {
     int64_t* o = p.stats + w * PGPU_NSTATS;
-    o[PGPU_STAT_MATCHED] = st.matched;
-    o[PGPU_STAT_SCANNED] = st.scanned;
-    o[PGPU_STAT_SECTOR_BYTES] = st.sector_bytes;
-    o[PGPU_STAT_DENSE_BYTES] = st.dense_bytes;
+    pub_store(p, &o[PGPU_STAT_MATCHED], st.matched);
+    pub_store(p, &o[PGPU_STAT_SCANNED], st.scanned);
+    pub_store(p, &o[PGPU_STAT_SECTOR_BYTES], st.sector_bytes);
+    pub_store(p, &o[PGPU_STAT_DENSE_BYTES], st.dense_bytes);
   }
   if (MODE == PGPU_MODE_AGG) {
     int64_t* slab = p.slab + w * p.nsec;
-    if (lane == 0) slab[0] = st.matched;
+    if (lane == 0) pub_store(p, &slab[0], st.matched);
     if (lane < p.nagg && p.aggs[lane].fn != PGPU_AGG_COUNT) {
       const int64_t* acc = (const int64_t*)(L.cons + (size_t)wave * p.cons_bytes + p.mask_rows * 256 +
                                             PGPU_CONS_LIST_BYTES_OF(0));
-      slab[p.aggs[lane].sec] = acc[lane];
+      pub_store(p, &slab[p.aggs[lane].sec], acc[lane]);
     }
   } else if (MODE == PGPU_MODE_LDS) {
     __syncthreads();
@@ -2618,6 +2628,148 @@ FI void direct_epilogue(const DevParams& p, const Lds& L, const Stats& st, int w
       p.rcount[(size_t)q * gridDim.x + blockIdx.x] = n < (uint32_t)p.rcap ? n : (uint32_t)p.rcap;
     }
   }
+}
+
+// Fused launch (p.fuse): finalize_kernel's work by the query kernel's last workgroup.  Called by every workgroup
+// after direct_epilogue: what it wrote for the last workgroup went out write-through (pub_store) or by device-scope
+// atomics (the table), so once every wave's stores have drained (vmcnt) and the workgroup has met at the barrier,
+// one relaxed agent-scope ticket publishes it; the workgroup that draws gridDim.x - 1 acquires and reduces the
+// per-wave statistics and the AGG slabs, turns the matched-segment words into pinned host flags and resets them, exports a non-AGG table, writes the next query's identities into the spare
+// table and resets the ticket.  No workgroup waits for another.  `smem` is the kernel's dynamic LDS (free by now;
+// PGPU_FUSE_LDS_BYTES of it: 256 reduction cells, then the "I am last" word).
+// The AGG slabs are reduced with finalize_kernel's tree -- thread t folds rows t, t + 256, ..., then the 256-wide
+// LDS tree -- so double sums are the same bits on both paths; the statistics are integer sums (any order is exact).
+template <int MODE>
+FI void fused_finalize(const DevParams& p, unsigned char* smem) {
+  static_assert(PGPU_DIRECT_THREADS == 256, "finalize_kernel's tree is 256 wide");
+  int64_t* red = (int64_t*)smem;
+  volatile uint32_t* is_last = (volatile uint32_t*)(smem + 2048);
+  const int tid = threadIdx.x;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();  // (also: every wave is done with the LDS table / accumulators)
+  if (tid == 0) {
+    const uint32_t t = __hip_atomic_fetch_add(p.fuse_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool last = t == gridDim.x - 1;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    *is_last = last ? 1u : 0u;
+  }
+  __syncthreads();
+  if (*is_last == 0u) return;
+  // One workgroup's loads are latency-bound (each dependent round trip costs 1-2 us under the other queries'
+  // streaming), so every phase issues FB independent loads per thread before it uses any, with clamped indices and
+  // selects behind the loads (a branch around a load would make each wait for the one before).
+  constexpr int FB = 8;
+  const int nslabs = p.fuse_nslabs;
+  typedef int64_t i64x2 __attribute__((ext_vector_type(2)));
+  // first batches of the three independent inputs, issued together: table words, segment words, statistics rows
+  int64_t tv[FB];
+  if (MODE != PGPU_MODE_AGG) {
+#pragma unroll
+    for (int j = 0; j < FB; ++j) {
+      const uint64_t i = (uint64_t)tid + 256u * j;
+      tv[j] = p.table[i < p.fuse_table_words ? i : 0];
+    }
+  }
+  const uint32_t sv0 = p.segany[tid < p.nseg ? tid : 0];
+  int64_t s[PGPU_NSTATS];
+#pragma unroll
+  for (int k = 0; k < PGPU_NSTATS; ++k) s[k] = 0;
+  static_assert(PGPU_NSTATS == 4, "statistics rows are read as two 16-byte halves");
+  for (int b0 = tid; b0 < nslabs; b0 += 256 * FB) {
+    i64x2 r[FB][2];
+#pragma unroll
+    for (int j = 0; j < FB; ++j) {
+      const int b = b0 + 256 * j;
+      const i64x2* row = (const i64x2*)(p.stats + (size_t)(b < nslabs ? b : 0) * PGPU_NSTATS);
+      r[j][0] = row[0];
+      r[j][1] = row[1];
+    }
+#pragma unroll
+    for (int j = 0; j < FB; ++j) {
+      const bool in = b0 + 256 * j < nslabs;
+      s[0] += in ? r[j][0].x : 0;
+      s[1] += in ? r[j][0].y : 0;
+      s[2] += in ? r[j][1].x : 0;
+      s[3] += in ? r[j][1].y : 0;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < PGPU_NSTATS; ++k) {
+    s[k] = wave_sum_i64(s[k]);
+    if ((tid & 63) == 0) red[(tid >> 6) * PGPU_NSTATS + k] = s[k];
+  }
+  __syncthreads();
+  if (tid < PGPU_NSTATS) {
+    int64_t v = 0;
+    for (int w = 0; w < PGPU_DIRECT_WAVES; ++w) v += red[w * PGPU_NSTATS + tid];
+    p.fuse_stats_out[tid] = v;
+  }
+  if (tid < p.nseg) {
+    p.fuse_seg_out[tid] = sv0 != 0u ? 1 : 0;
+    p.segany[tid] = 0u;
+  }
+  for (int i = tid + 256; i < p.nseg; i += 256) {
+    p.fuse_seg_out[i] = p.segany[i] != 0u ? 1 : 0;
+    p.segany[i] = 0u;
+  }
+  if (MODE != PGPU_MODE_AGG) {
+#pragma unroll
+    for (int j = 0; j < FB; ++j) {
+      const uint64_t i = (uint64_t)tid + 256u * j;
+      if (i < p.fuse_table_words) p.fuse_host_table[i] = tv[j];
+    }
+    for (uint64_t i0 = (uint64_t)tid + 256u * FB; i0 < p.fuse_table_words; i0 += 256u * FB) {
+#pragma unroll
+      for (int j = 0; j < FB; ++j) {
+        const uint64_t i = i0 + 256u * j;
+        tv[j] = p.table[i < p.fuse_table_words ? i : 0];
+      }
+#pragma unroll
+      for (int j = 0; j < FB; ++j) {
+        const uint64_t i = i0 + 256u * j;
+        if (i < p.fuse_table_words) p.fuse_host_table[i] = tv[j];
+      }
+    }
+    if (p.fuse_spare)
+      for (int sc = 0; sc < p.nsec; ++sc) {
+        const int64_t idv = sec_identity(p.sec_op[sc]);
+        int64_t* dst = p.fuse_spare + (size_t)sc * p.G;
+        for (uint64_t k = tid; k < p.G; k += 256) dst[k] = idv;
+      }
+  } else {
+    // AGG slabs: column by column with finalize_kernel's tree (rows t, t + 256, ... folded in that order)
+    for (int col = 0; col < p.nsec; ++col) {
+      const int op = p.sec_op[col];
+      const int64_t* src = p.slab + col;
+      int64_t v = sec_identity(op);
+      for (int b0 = tid; b0 < nslabs; b0 += 256 * FB) {
+        int64_t r[FB];
+#pragma unroll
+        for (int j = 0; j < FB; ++j) {
+          const int b = b0 + 256 * j;
+          r[j] = src[(size_t)(b < nslabs ? b : 0) * p.nsec];
+        }
+#pragma unroll
+        for (int j = 0; j < FB; ++j)
+          if (b0 + 256 * j < nslabs) v = cell_combine(op, v, r[j]);
+      }
+      __syncthreads();  // (the statistics' / the previous column's cells have been read)
+      red[tid] = v;
+      __syncthreads();
+      for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] = cell_combine(op, red[tid], red[tid + o]);
+        __syncthreads();
+      }
+      if (tid == 0) {
+        p.table[col] = red[0];
+        if (p.fuse_host_table) p.fuse_host_table[col] = red[0];
+      }
+    }
+  }
+  if (tid == 0) *p.fuse_ticket = 0u;
 }
 
 // ================================================================================================================
@@ -2834,6 +2986,8 @@ __global__ __launch_bounds__(PGPU_DIRECT_THREADS) void query_kernel_rdirect(DevP
 #endif
   const Stats st = rdirect_consumer<MODE, PL, PK>(p, L, wave, t0, t1 - t0, pf);
   direct_epilogue<MODE>(p, L, st, wave, lane, pf);
+  if constexpr (MODE == PGPU_MODE_AGG || MODE == PGPU_MODE_LDS || MODE == PGPU_MODE_GLOBAL)
+    if (p.fuse) fused_finalize<MODE>(p, dyn_smem);
 }
 
 // ================================================================================================================
@@ -5505,16 +5659,21 @@ static hipError_t rd_attr(size_t lds_bytes) {
 }
 // (the prefix variants stop at 12 planes: 16 + 3 planes per tile in flight would pass 128 VGPRs -- one wave per
 // SIMD less -- so the runtime sets rd_pfx only for fast leaves of <= 12 bits)
+// ev0 / ev1 (both or neither): recorded at the kernel's start and end by its own dispatch packet, instead of two
+// hipEventRecord packets around it (the fused launch, where the kernel is all the events span)
 template <int M, int PK>
-static void rd_launch(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st) {
-  if (p.rd_planes <= 8)
-    hipLaunchKernelGGL((query_kernel_rdirect<M, 8, PK>), dim3(grid), dim3(PGPU_DIRECT_THREADS), dyn_smem, st, p);
-  else if (p.rd_planes <= 10)
-    hipLaunchKernelGGL((query_kernel_rdirect<M, 10, PK>), dim3(grid), dim3(PGPU_DIRECT_THREADS), dyn_smem, st, p);
-  else if (PK > 0 || p.rd_planes <= 12)
-    hipLaunchKernelGGL((query_kernel_rdirect<M, 12, PK>), dim3(grid), dim3(PGPU_DIRECT_THREADS), dyn_smem, st, p);
-  else
-    hipLaunchKernelGGL((query_kernel_rdirect<M, 16, 0>), dim3(grid), dim3(PGPU_DIRECT_THREADS), dyn_smem, st, p);
+static void rd_launch(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+  const dim3 g(grid), b(PGPU_DIRECT_THREADS);
+#define RD_GO(PL, K)                                                                                       \
+  do {                                                                                                     \
+    if (ev0) hipExtLaunchKernelGGL((query_kernel_rdirect<M, PL, K>), g, b, dyn_smem, st, ev0, ev1, 0, p);  \
+    else hipLaunchKernelGGL((query_kernel_rdirect<M, PL, K>), g, b, dyn_smem, st, p);                      \
+  } while (0)
+  if (p.rd_planes <= 8) RD_GO(8, PK);
+  else if (p.rd_planes <= 10) RD_GO(10, PK);
+  else if (PK > 0 || p.rd_planes <= 12) RD_GO(12, PK);
+  else RD_GO(16, 0);
+#undef RD_GO
 }
 template <int M, int PK>
 static hipError_t rd_attrs(size_t lds_bytes) {
@@ -5620,7 +5779,8 @@ template <int M>
     else hipLaunchKernelGGL((query_kernel<M, 0>), dim3(grid), dim3(PGPU_THREADS(0)), dyn_smem, st, p);           \
     return hipGetLastError();                                                                                   \
   }                                                                                                             \
-  hipError_t pgpu_launch_direct_##NAME(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st) {         \
+  hipError_t pgpu_launch_direct_##NAME(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st,          \
+                                       hipEvent_t ev0, hipEvent_t ev1) {                                        \
     if (p.direct == 6) {                                                                                        \
       if constexpr (M != PGPU_MODE_PART)                                                                        \
         hipLaunchKernelGGL((query_kernel_cand<M>), dim3(grid), dim3(PGPU_DIRECT_THREADS), dyn_smem, st, p);     \
@@ -5636,8 +5796,8 @@ template <int M>
       } else                                                                                                    \
         return hipErrorInvalidValue;                                                                            \
     } else if (p.direct == 2) {                                                                                 \
-      if (p.rd_pfx) rd_launch<M, PGPU_PFX_PLANES>(p, grid, dyn_smem, st);                                       \
-      else rd_launch<M, 0>(p, grid, dyn_smem, st);                                                              \
+      if (p.rd_pfx) rd_launch<M, PGPU_PFX_PLANES>(p, grid, dyn_smem, st, ev0, ev1);                             \
+      else rd_launch<M, 0>(p, grid, dyn_smem, st, ev0, ev1);                                                    \
     } else                                                                                                      \
       hipLaunchKernelGGL((query_kernel_direct<M>), dim3(grid), dim3(PGPU_DIRECT_THREADS), dyn_smem, st, p);     \
     return hipGetLastError();                                                                                   \
@@ -5667,7 +5827,8 @@ template <int M>
   }
 #define PGPU_MODE_DECLS(NAME)                                                                   \
   hipError_t pgpu_launch_query_##NAME(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st);  \
-  hipError_t pgpu_launch_direct_##NAME(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st); \
+  hipError_t pgpu_launch_direct_##NAME(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st, \
+                                       hipEvent_t ev0, hipEvent_t ev1);                                \
   hipError_t pgpu_prepare_##NAME(size_t lds_bytes);
 PGPU_MODE_DECLS(agg) PGPU_MODE_DECLS(lds) PGPU_MODE_DECLS(global) PGPU_MODE_DECLS(part) PGPU_MODE_DECLS(hash)
 
@@ -6082,13 +6243,15 @@ hipError_t pgpu_launch_query(const DevParams& p, int grid, size_t dyn_smem, hipS
 }
 
 // Direct variant (p.direct): PGPU_DIRECT_THREADS per workgroup, several workgroups per CU.
-hipError_t pgpu_launch_query_direct(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st) {
+// ev0 / ev1: see rd_launch (register-direct kernels only; the others ignore them -- their callers pass none)
+hipError_t pgpu_launch_query_direct(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st, hipEvent_t ev0,
+                                    hipEvent_t ev1) {
   switch (p.mode) {
-    case PGPU_MODE_AGG: return pgpu_launch_direct_agg(p, grid, dyn_smem, st);
-    case PGPU_MODE_LDS: return pgpu_launch_direct_lds(p, grid, dyn_smem, st);
-    case PGPU_MODE_GLOBAL: return pgpu_launch_direct_global(p, grid, dyn_smem, st);
-    case PGPU_MODE_PART: return pgpu_launch_direct_part(p, grid, dyn_smem, st);
-    case PGPU_MODE_HASH: return pgpu_launch_direct_hash(p, grid, dyn_smem, st);
+    case PGPU_MODE_AGG: return pgpu_launch_direct_agg(p, grid, dyn_smem, st, ev0, ev1);
+    case PGPU_MODE_LDS: return pgpu_launch_direct_lds(p, grid, dyn_smem, st, ev0, ev1);
+    case PGPU_MODE_GLOBAL: return pgpu_launch_direct_global(p, grid, dyn_smem, st, ev0, ev1);
+    case PGPU_MODE_PART: return pgpu_launch_direct_part(p, grid, dyn_smem, st, ev0, ev1);
+    case PGPU_MODE_HASH: return pgpu_launch_direct_hash(p, grid, dyn_smem, st, ev0, ev1);
     default: return hipErrorInvalidValue;
   }
 }

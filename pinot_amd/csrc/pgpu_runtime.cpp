@@ -35,7 +35,8 @@
 hipError_t pgpu_prepare_query_kernels(size_t lds_bytes);
 hipError_t pgpu_launch_table_init(const DevParams& p, hipStream_t st);
 hipError_t pgpu_launch_query(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st);
-hipError_t pgpu_launch_query_direct(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st);
+hipError_t pgpu_launch_query_direct(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st,
+                                    hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 bool pgpu_pscan_prefetch_ok(int kb, int vb);
 hipError_t pgpu_launch_finalize(const DevParams& p, int nslabs, int64_t* stats_out, uint8_t* seg_out,
                                 int64_t* host_table, uint64_t table_words, hipStream_t st);
@@ -295,6 +296,20 @@ struct Workspace {
   DevMem d_cancel;                     // cancel word (DevParams::cancel): = the query's generation -> stop
   PinnedMem h_cancel;                  // its source for pgpu_query_cancel's copy-engine write
   uint32_t cancel_gen = 0;
+  // Fused launch (launch_impl): the ticket word of fused_finalize (zero between queries); a host shadow of the
+  // bytes the device arena holds (empty: unknown -- dropped whenever `arena` is reallocated), so that a query
+  // packing the same bytes skips the copy; and, on the workspace owning the table, a second table that the previous
+  // fused query filled with the identities of the layout `spare_sig` describes (the next one with that layout takes
+  // it as its table and the two swap roles).
+  DevMem ticket;
+  std::vector<char> arena_shadow;
+  DevMem spare;
+  struct SpareSig {
+    bool valid = false;
+    uint64_t G = 0;
+    int32_t nsec = 0, mode = 0;
+    int32_t ops[PGPU_MAX_SECTIONS] = {};
+  } spare_sig;
   bool busy = false;
   ~Workspace() {
     if (ev0) (void)hipEventDestroy(ev0);
@@ -2797,9 +2812,11 @@ int enqueue_compact(pgpu_context* ctx, Workspace* ws, const pgpu_table_layout* L
 
 // eager: compact the table (only the best groups by eager_order, when given) on the query's stream right behind
 // its kernels, into the workspace; pgpu_query_collect then only copies the rows out (pgpu_query_submit_ordered)
+// tws (pgpu_query_submit*): the workspace owning dev_table (its `table`); with it a register-direct query with a small
+// table runs as one launch (see Workspace::ticket) and may take the workspace's spare table as its table
 static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream, void* dev_table,
                        uint64_t table_bytes, int64_t* host_table, pgpu_query** out_query, bool eager = false,
-                       const pgpu_topk* eager_order = nullptr) {
+                       const pgpu_topk* eager_order = nullptr, Workspace* tws = nullptr) {
   if (!ctx || !q || !out_query) return fail(PGPU_E_INVALID, "null argument");
   pgpu_table_layout L;
   int rc = pgpu_table_layout_of(q, &L);
@@ -3388,6 +3405,7 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
     // a bail after the query kernel was enqueued but before finalize_kernel: the matched-segment words it may
     // have set must not count towards the workspace's next query (they are zero between queries)
     if (bail_stream && ws->segany.p) (void)hipMemsetAsync(ws->segany.p, 0, ws->segany.n, bail_stream);
+    if (bail_stream && ws->ticket.p) (void)hipMemsetAsync(ws->ticket.p, 0, ws->ticket.n, bail_stream);
     release_ws(ctx, ws);
     return code;
   };
@@ -3423,7 +3441,10 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
   const size_t o_cand = align16(o_jobs + pk.jobs.size() * sizeof(ProgJob));
   const size_t total = align16(o_cand + pk.cand.size() * 4) + 16;
   hipError_t e = ws->h_arena.ensure(total);
+  const void* arena_p0 = ws->arena.p;
+  const size_t arena_n0 = ws->arena.n;
   if (e == hipSuccess) e = ws->arena.ensure(total, ctx->mpool, st);
+  if (ws->arena.p != arena_p0 || ws->arena.n != arena_n0) ws->arena_shadow.clear();
   if (e == hipSuccess) e = ws->slab.ensure(8ull * nwaves * L.num_sections + 16, ctx->mpool, st);
   if (e == hipSuccess) e = ws->stats.ensure(8ull * nwaves * PGPU_NSTATS + 16, ctx->mpool, st);
   if (e == hipSuccess) e = ws->stats_out.ensure(8 * PGPU_NSTATS, ctx->mpool, st);
@@ -3615,71 +3636,148 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
   if (expired) e = hipMemsetD32Async((hipDeviceptr_t)ws->d_cancel.p, (int)ws->cancel_gen, 1, st);
   if (e == hipSuccess) e = ws->h_arena.device_ptr(&h_arena_dev);
   if (e == hipSuccess) e = ws->h_stats.device_ptr(&h_stats_dev);
-  if (e == hipSuccess) e = pgpu_launch_prologue(p, h_arena_dev, ws->arena.p, total, p.mode != PGPU_MODE_AGG, st);
-  if (e == hipSuccess) e = hipEventRecord(ws->ev0, st);
-  // raw-value leaves' match bitmaps (timed with the query: they are part of its filter)
-  if (e == hipSuccess && !pk.raws.empty())
-    e = pgpu_launch_rawpred((const RawLeaf*)(d + o_raw), (int)pk.raws.size(), max_raw_words, st);
-  if (e == hipSuccess && !pk.mvs.empty())
-    e = pgpu_launch_mvpred((const MvLeaf*)(d + o_mv), (int)pk.mvs.size(), max_mv_words, st);
   p.invx = (const InvLeafX*)(d + o_inv);
   bool expand = false;  // (query_kernel_rkey and query_kernel_cand read their leaves' containers themselves)
   for (const InvLeafX& x : pk.invx) expand |= !x.skip;
-  if (e == hipSuccess && expand && p.direct != 5)
-    e = pgpu_launch_invexp((const InvLeafX*)(d + o_inv), (int)pk.invx.size(), max_inv_words, st);
-  if (e == hipSuccess && p.direct == 5) {
-    int64_t max_pairs = 0;
-    for (const InvLeafX& x : pk.invx) max_pairs = std::max<int64_t>(max_pairs, (int64_t)x.nids * x.nkeys);
-    e = pgpu_launch_rkey_ctab((const InvLeafX*)(d + o_inv), (int)pk.invx.size(), max_pairs,
-                              (DevContainer*)ws->rkctab.p, st);
-  }
-  if (e == hipSuccess && !pk.jobs.empty())
-    e = pgpu_launch_progbits(p, (const ProgJob*)(d + o_jobs), (int)pk.jobs.size(), pk.job_tiles, st);
-  if (e == hipSuccess)
-    e = p.pscan ? pgpu_launch_part_scan(p, grid, dyn, st)
-                : (p.direct ? pgpu_launch_query_direct(p, grid, dyn, st) : pgpu_launch_query(p, grid, dyn, st));
-  if (e == hipSuccess && p.mode == PGPU_MODE_PART) e = pgpu_launch_part_reduce(p, grid, st);
-  // the reference's filter statistic (andfsm maps or leaf bitmaps for the host replay) is part of the query's
-  // kernels: ev0 .. ev1 spans every kernel that reads the segments, so kernel_ms prices the whole step's reads
-  if (e == hipSuccess && pk.fsm) {
-    void* h_ent_dev = nullptr;
-    e = ws->h_fsment.device_ptr(&h_ent_dev);
-    if (e == hipSuccess) e = pgpu_launch_andfsm(p, pk.fsm_s2, (uint32_t*)ws->fsmfn.p, (int64_t*)h_ent_dev, st);
-  }
-  if (e == hipSuccess && pk.leaf_words > 0) e = pgpu_launch_leafbits(p, st);
-  if (e == hipSuccess) e = hipEventRecord(ws->ev1, st);
-  // statistics, numSegmentsMatched flags and a small table into pinned host memory: one launch
-  if (e == hipSuccess) {
-    void* h_seg_dev = nullptr;
-    e = ws->h_segany.device_ptr(&h_seg_dev);
-    if (e == hipSuccess)
-      e = pgpu_launch_finalize(p, nwaves, (int64_t*)h_stats_dev, (uint8_t*)h_seg_dev, host_table,
-                               host_table ? pgpu_table_bytes(&L) / 8 : 0, st);
-  }
-  if (e == hipSuccess && p.mode == PGPU_MODE_HASH) {
-    // probe-overflow flag and the tracked segments' distinct-key counts, into pinned host memory
-    void* h_cnt_dev = nullptr;
-    if (p.segmask_rows) {
-      e = ws->h_segcnt.device_ptr(&h_cnt_dev);
-      if (e == hipSuccess) e = pgpu_launch_segcount(p, (int64_t*)h_cnt_dev, st);
+  // One launch instead of three (prologue, query kernel, finalize): a submitted register-direct query with a small
+  // table and no kernel before or behind the query kernel.  Its last workgroup does finalize_kernel's work
+  // (fused_finalize); the arena is copied only when its bytes differ from what the device holds; a table that
+  // needs identities is the workspace's spare table when the previous fused query prepared it for this layout.
+  // PGPU_Q_SPLIT_LAUNCH (PGPU_SPLIT_LAUNCH=1: every query) keeps the three launches.
+  static const bool env_split = getenv("PGPU_SPLIT_LAUNCH") && atoi(getenv("PGPU_SPLIT_LAUNCH")) != 0;
+  const uint64_t table_words = pgpu_table_bytes(&L) / 8;
+  const char* split_why = nullptr;  // why the query keeps the three launches (PGPU_PLAN_TRACE)
+  if (!tws) split_why = "external stream or table";
+  else if (env_split || (q->flags & PGPU_Q_SPLIT_LAUNCH)) split_why = "forced";
+  else if (!host_table || eager || (q->flags & PGPU_Q_FOLD)) split_why = "table not exported whole";
+  else if (p.direct != 2 || p.pscan ||
+           !(p.mode == PGPU_MODE_AGG || p.mode == PGPU_MODE_LDS || p.mode == PGPU_MODE_GLOBAL))
+    split_why = "not a register-direct AGG / LDS / GLOBAL query";
+  else if (pk.fsm || pk.leaf_words > 0 || !pk.raws.empty() || !pk.mvs.empty() || expand || !pk.jobs.empty())
+    split_why = "kernels before or behind the query kernel";
+  else if (dyn < PGPU_FUSE_LDS_BYTES || table_words != (uint64_t)p.nsec * p.G ||
+           table_words > PGPU_FUSE_MAX_TABLE_WORDS)
+    split_why = "table too large for one workgroup's epilogue";
+  const bool fuse = split_why == nullptr;
+  bool kernel_is_done = false;  // the query kernel's own end event also says the query is complete
+  if (fuse) {
+    if (e == hipSuccess && !ws->ticket.p) {
+      e = ws->ticket.ensure(16, ctx->mpool, st);
+      if (e == hipSuccess) e = hipMemsetAsync(ws->ticket.p, 0, ws->ticket.n, st);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync((char*)ws->h_stats.p + 8 * PGPU_NSTATS, ws->hflag.p, 4, hipMemcpyDeviceToHost, st);
-  }
-  if (e == hipSuccess && pk.leaf_words > 0)
-    e = hipMemcpyAsync(ws->h_leafbits.p, ws->leafbits.p, 4ull * pk.leaf_words, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && eager) {
-    const int crc = enqueue_compact(ctx, ws, &L, dev_table, st, eager_order);
-    if (crc) return bail(crc);
+    void* h_seg_dev = nullptr;
+    if (e == hipSuccess) e = ws->h_segany.device_ptr(&h_seg_dev);
+    bool init_table = p.mode != PGPU_MODE_AGG, spare_hit = false;
+    if (e == hipSuccess && init_table) {
+      Workspace::SpareSig& sg = tws->spare_sig;
+      spare_hit = sg.valid && tws->spare.n >= need && sg.G == p.G && sg.nsec == p.nsec && sg.mode == p.mode &&
+                  memcmp(sg.ops, p.sec_op, sizeof(int32_t) * p.nsec) == 0;
+      if (spare_hit) {
+        std::swap(tws->table, tws->spare);
+        p.table = (int64_t*)tws->table.p;
+        init_table = false;
+      }
+      sg.valid = false;  // (until this query's kernel is enqueued: it writes the spare)
+      e = tws->spare.ensure(need, ctx->mpool, st);
+      p.fuse_spare = (int64_t*)tws->spare.p;
+    }
+    const bool copy = ws->arena_shadow.size() != total || memcmp(ws->arena_shadow.data(), h, total) != 0;
+    if (copy) ws->arena_shadow.assign(h, h + total);
+    p.fuse = 1;
+    p.fuse_nslabs = nwaves;
+    p.fuse_ticket = (uint32_t*)ws->ticket.p;
+    p.fuse_stats_out = (int64_t*)h_stats_dev;
+    p.fuse_seg_out = (uint8_t*)h_seg_dev;
+    p.fuse_host_table = host_table;
+    p.fuse_table_words = p.mode != PGPU_MODE_AGG ? table_words : 0;
+    if (trace)
+      fprintf(stderr, "[pgpu plan] launch fused: arena %s, table %s\n", copy ? "copied" : "resident",
+              p.mode == PGPU_MODE_AGG ? "needs no identities" : (spare_hit ? "spare" : "initialised"));
+    if (e == hipSuccess && (copy || init_table))
+      e = pgpu_launch_prologue(p, h_arena_dev, ws->arena.p, copy ? total : 0, init_table, st);
+    if (e != hipSuccess) ws->arena_shadow.clear();
+    // ev0 .. ev1 spans this one kernel: its dispatch packet records both (no event packets around it)
+    static const bool ext_events = !(getenv("PGPU_FUSE_EVENT_PACKETS") && atoi(getenv("PGPU_FUSE_EVENT_PACKETS")) != 0);
+    if (e == hipSuccess && !ext_events) e = hipEventRecord(ws->ev0, st);
+    if (e == hipSuccess)
+      e = ext_events ? pgpu_launch_query_direct(p, grid, dyn, st, ws->ev0, ws->ev1)
+                     : pgpu_launch_query_direct(p, grid, dyn, st);
+    if (e == hipSuccess && p.fuse_spare) {
+      Workspace::SpareSig& sg = tws->spare_sig;
+      sg.valid = true;
+      sg.G = p.G;
+      sg.nsec = p.nsec;
+      sg.mode = p.mode;
+      memcpy(sg.ops, p.sec_op, sizeof(int32_t) * p.nsec);
+    }
+    if (e == hipSuccess && !ext_events) e = hipEventRecord(ws->ev1, st);
+    kernel_is_done = ext_events;  // (nothing is enqueued behind the kernel: no third packet either)
+  } else {
+    if (trace) fprintf(stderr, "[pgpu plan] launch split (%s): prologue, query kernels, finalize\n", split_why);
+    ws->arena_shadow.clear();  // (the prologue below rewrites the arena; this path keeps no shadow)
+    if (e == hipSuccess) e = pgpu_launch_prologue(p, h_arena_dev, ws->arena.p, total, p.mode != PGPU_MODE_AGG, st);
+    if (e == hipSuccess) e = hipEventRecord(ws->ev0, st);
+    // raw-value leaves' match bitmaps (timed with the query: they are part of its filter)
+    if (e == hipSuccess && !pk.raws.empty())
+      e = pgpu_launch_rawpred((const RawLeaf*)(d + o_raw), (int)pk.raws.size(), max_raw_words, st);
+    if (e == hipSuccess && !pk.mvs.empty())
+      e = pgpu_launch_mvpred((const MvLeaf*)(d + o_mv), (int)pk.mvs.size(), max_mv_words, st);
+    if (e == hipSuccess && expand && p.direct != 5)
+      e = pgpu_launch_invexp((const InvLeafX*)(d + o_inv), (int)pk.invx.size(), max_inv_words, st);
+    if (e == hipSuccess && p.direct == 5) {
+      int64_t max_pairs = 0;
+      for (const InvLeafX& x : pk.invx) max_pairs = std::max<int64_t>(max_pairs, (int64_t)x.nids * x.nkeys);
+      e = pgpu_launch_rkey_ctab((const InvLeafX*)(d + o_inv), (int)pk.invx.size(), max_pairs,
+                                (DevContainer*)ws->rkctab.p, st);
+    }
+    if (e == hipSuccess && !pk.jobs.empty())
+      e = pgpu_launch_progbits(p, (const ProgJob*)(d + o_jobs), (int)pk.jobs.size(), pk.job_tiles, st);
+    if (e == hipSuccess)
+      e = p.pscan ? pgpu_launch_part_scan(p, grid, dyn, st)
+                  : (p.direct ? pgpu_launch_query_direct(p, grid, dyn, st) : pgpu_launch_query(p, grid, dyn, st));
+    if (e == hipSuccess && p.mode == PGPU_MODE_PART) e = pgpu_launch_part_reduce(p, grid, st);
+    // the reference's filter statistic (andfsm maps or leaf bitmaps for the host replay) is part of the query's
+    // kernels: ev0 .. ev1 spans every kernel that reads the segments, so kernel_ms prices the whole step's reads
+    if (e == hipSuccess && pk.fsm) {
+      void* h_ent_dev = nullptr;
+      e = ws->h_fsment.device_ptr(&h_ent_dev);
+      if (e == hipSuccess) e = pgpu_launch_andfsm(p, pk.fsm_s2, (uint32_t*)ws->fsmfn.p, (int64_t*)h_ent_dev, st);
+    }
+    if (e == hipSuccess && pk.leaf_words > 0) e = pgpu_launch_leafbits(p, st);
+    if (e == hipSuccess) e = hipEventRecord(ws->ev1, st);
+    // statistics, numSegmentsMatched flags and a small table into pinned host memory: one launch
+    if (e == hipSuccess) {
+      void* h_seg_dev = nullptr;
+      e = ws->h_segany.device_ptr(&h_seg_dev);
+      if (e == hipSuccess)
+        e = pgpu_launch_finalize(p, nwaves, (int64_t*)h_stats_dev, (uint8_t*)h_seg_dev, host_table,
+                                 host_table ? pgpu_table_bytes(&L) / 8 : 0, st);
+    }
+    if (e == hipSuccess && p.mode == PGPU_MODE_HASH) {
+      // probe-overflow flag and the tracked segments' distinct-key counts, into pinned host memory
+      void* h_cnt_dev = nullptr;
+      if (p.segmask_rows) {
+        e = ws->h_segcnt.device_ptr(&h_cnt_dev);
+        if (e == hipSuccess) e = pgpu_launch_segcount(p, (int64_t*)h_cnt_dev, st);
+      }
+      if (e == hipSuccess) e = hipMemcpyAsync((char*)ws->h_stats.p + 8 * PGPU_NSTATS, ws->hflag.p, 4, hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess && pk.leaf_words > 0)
+      e = hipMemcpyAsync(ws->h_leafbits.p, ws->leafbits.p, 4ull * pk.leaf_words, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && eager) {
+      const int crc = enqueue_compact(ctx, ws, &L, dev_table, st, eager_order);
+      if (crc) return bail(crc);
+    }
   }
   // completion of this query alone (later queries may already be queued behind it on the same stream)
-  if (e == hipSuccess) e = hipEventRecord(ws->done, st);
+  if (e == hipSuccess && !kernel_is_done) e = hipEventRecord(ws->done, st);
   if (e != hipSuccess) return bail(fail(PGPU_E_HIP, "query launch: %s", hipGetErrorString(e)));
 
   host_timing().add(4, tl0, HostTiming::us());
   auto* qq = new pgpu_query();
   qq->ctx = ctx;
   qq->ws = ws;
-  qq->done = ws->done;
+  qq->done = kernel_is_done ? ws->ev1 : ws->done;
   qq->eager = eager;
   qq->stream = st;
   qq->params = p;
@@ -4598,7 +4696,7 @@ static int submit_impl(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_t
   // another order still selects from it)
   const bool ordered = order && order->k > 0 && L.num_keys > order->k;
   rc = launch_impl(ctx, q, ctx->qstream, tws->table.p, tws->table.n, (int64_t*)h_table_dev, &qq, !small && !folded,
-                   ordered ? order : nullptr);
+                   ordered ? order : nullptr, tws);
   if (rc) {
     release_ws(ctx, tws);
     return rc;
