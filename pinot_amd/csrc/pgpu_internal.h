@@ -160,15 +160,15 @@ struct DevSeg {
   int32_t nvstage;
   int32_t vstage_col[2];
   int32_t vstage_off[2];
-  // index-only dense program as a truth table (register streaming, DevParams::direct == 4): bit t = the program's
+  // index-only dense program as a truth table (register streaming, DevParams::direct == PGPU_KV_RPROG): bit t = the program's
   // result when leaf i has the value of bit i of t; leaves 0 .. nbits - 1 are the BITS slots, then the SORTED leaves
   // at instruction indexes psorted[0 .. pnsorted) (absolute, into DevParams::instrs)
   uint32_t ptt;
   int32_t pnsorted;
   int32_t psorted[2];
-  // query_kernel_rkey (DevParams::direct == 5): the segment's first (segment, container key) unit, and for each BITS
+  // query_kernel_rkey (DevParams::direct == PGPU_KV_RKEY): the segment's first (segment, container key) unit, and for each BITS
   // slot the inverted leaf it stands for (index into DevParams::invx)
-  // query_kernel_cand (direct == 6) units are the containers of the leading inverted leaf (or the sorted leaf's
+  // query_kernel_cand (direct == PGPU_KV_CAND) units are the containers of the leading inverted leaf (or the sorted leaf's
   // ranges) instead: unit_begin is the segment's first, cand_leaf the inverted leaf (index into DevParams::invx; -1
   // for a sorted one)
   int32_t unit_begin;
@@ -389,7 +389,7 @@ struct DevParams {
                                   // filter, one group column): phase 1 reads the next tile's words a step ahead
   int32_t mask_rows;              // mask rows per consumer (filter slots used + 1 scratch row)
   int32_t cons_bytes;             // PGPU_CONS_BYTES(dense, mask_rows)
-  int32_t direct;                 // query_kernel_direct: self-loading waves (every staged column a sliced fast leaf)
+  int32_t direct;                 // the query kernel variant, a PGPU_KV_* of pinot_gpu.h (PGPU_KV_PSCAN is never stored here: pscan > 0 says so)
   int32_t dslots;                 // direct: LDS slots per wave (dslots - 1 tiles in flight while one is filtered)
   int32_t min_instrs;             // direct: fewest DMA instructions of any segment's tile (counted vmcnt waits)
   // PART with one-word records: ldict = phase 2 reads SUM values from pdict copied into LDS beside its table
@@ -428,7 +428,7 @@ struct DevParams {
   int32_t rd_planes;              // register-direct: planes per tile held in VGPRs (>= every leaf's width; 8/10/12/16)
   int32_t mv_gmask;               // bit g: group column g is multi-value (sparse_agg_mv expands each doc's values)
   int32_t rd_pfx;                 // register-direct: prefix planes of every segment's residual leaf (0 or PGPU_PFX_PLANES)
-  int32_t rs_vplanes;             // register streaming (direct == 3): value planes held per tile (16 or 24)
+  int32_t rs_vplanes;             // register streaming (direct == PGPU_KV_RSTREAM): value planes held per tile (16 or 24)
   int32_t total_units;            // query_kernel_rkey: (segment, 65,536-doc container key) units; query_kernel_cand:
                                   // (segment, container) units
   int32_t rk_leaves;              // query_kernel_rkey: leaf images per LDS buffer (max BITS slots of a segment)
@@ -437,7 +437,7 @@ struct DevParams {
   const struct DevContainer* rk_ctab;  // query_kernel_rkey: container record per (leaf, id, key) (rkey_ctab_kernel)
   const uint32_t* cand_ct;        // query_kernel_cand: per unit {segment, its container's index in InvLeafX::ct
                                   // (~0u: a sorted leaf's doc range), first doc, last doc}
-  uint32_t* fsm_fn;               // query_kernel_rfsm (direct == 8): per-tile transducer maps for andfsm_segment_kernel
+  uint32_t* fsm_fn;               // query_kernel_rfsm (direct == PGPU_KV_RFSM): per-tile transducer maps for andfsm_segment_kernel
   // Fused launch (query_kernel_rdirect of a submitted query with a small table): every workgroup takes a ticket
   // after its epilogue and the one that draws gridDim.x - 1 does finalize_kernel's work (fused_finalize), then
   // writes the identities of this layout into the workspace's spare table for the next query.  fuse == 0: the

@@ -2773,7 +2773,7 @@ FI void fused_finalize(const DevParams& p, unsigned char* smem) {
 }
 
 // ================================================================================================================
-// REGISTER-DIRECT variant (p.direct == 2): every segment's only staged column is one bit-sliced fast leaf of at most
+// REGISTER-DIRECT variant (p.direct == PGPU_KV_RDIRECT): every segment's only staged column is one bit-sliced fast leaf of at most
 // PL = p.rd_planes bits (8, 10, 12 or 16: the borrow chains cost one v_bitop3 per plane, so PL tracks the width).  Its planes go straight into VGPRs -- plane k of lane l is one coalesced 4-B load per
 // lane, 256 B per wave-instruction -- with RD tiles in flight per wave (a register ring, unrolled), no LDS staging
 // at all: tools/stream_bench.hip reads such a stream at 5.6-6.0 TB/s where the LDS-DMA self-loading kernel
@@ -2991,7 +2991,7 @@ __global__ __launch_bounds__(PGPU_DIRECT_THREADS) void query_kernel_rdirect(DevP
 }
 
 // ================================================================================================================
-// EXACT FILTER STATISTICS IN THE REGISTER STREAM (p.direct == 8).  With the reference's numEntriesScannedInFilter
+// EXACT FILTER STATISTICS IN THE REGISTER STREAM (p.direct == PGPU_KV_RFSM).  With the reference's numEntriesScannedInFilter
 // requested and every segment's filter an AND of two bit-sliced scan leaves (config 5's shape), the count needs each
 // leaf's match word at every doc (AndDocIdIterator.java:40-67 leap-frogs SVScanDocIdIterator.java:57-71 over both
 // leaves), so both leaves' planes are streamed in full anyway.  This kernel streams them once -- RD tiles ahead in a
@@ -3225,7 +3225,7 @@ __global__ __launch_bounds__(PGPU_DIRECT_THREADS) void query_kernel_rfsm(DevPara
 }
 
 // ================================================================================================================
-// REGISTER STREAMING (p.direct == 3, aggregation-only mode): every segment's filter is an AND of two bit-sliced fast
+// REGISTER STREAMING (p.direct == PGPU_KV_RSTREAM, aggregation-only mode): every segment's filter is an AND of two bit-sliced fast
 // leaves -- one of <= 16 bits ("wide"), one of <= PN bits ("narrow") -- and every aggregation is answered from one
 // column's value planes (PGPU_AM_SLICED, no residual program).  All three plane sets of a tile stream into VGPRs
 // RD tiles ahead, so the aggregation reads registers that were loaded with the filter planes: no LDS slot, no
@@ -3449,7 +3449,7 @@ __global__ __launch_bounds__(PGPU_DIRECT_THREADS) void query_kernel_rstream(DevP
 }
 
 // ================================================================================================================
-// REGISTER STREAMING OF INDEX-ONLY PROGRAMS (p.direct == 4, aggregation-only mode): every segment's dense program
+// REGISTER STREAMING OF INDEX-ONLY PROGRAMS (p.direct == PGPU_KV_RPROG, aggregation-only mode): every segment's dense program
 // reads only precomputed bitmaps (BITS leaves: inverted-index leaves expanded by invexp_kernel, raw-value leaves)
 // and sorted-column doc ranges, <= 5 leaves, none counted as scanned entries; its aggregations come from <= 2
 // columns' value planes.  The runtime turns the program into a truth table over its leaves (DevSeg::ptt), so a
@@ -3650,7 +3650,7 @@ __global__ __launch_bounds__(PGPU_DIRECT_THREADS) void query_kernel_rprog(DevPar
 }
 
 // ================================================================================================================
-// INDEX-ONLY PROGRAMS OVER ROARING CONTAINERS IN LDS (p.direct == 5): query_kernel_rprog's shape when every BITS
+// INDEX-ONLY PROGRAMS OVER ROARING CONTAINERS IN LDS (p.direct == PGPU_KV_RKEY): query_kernel_rprog's shape when every BITS
 // leaf of every segment is an inverted-index leaf.  Instead of expanding those leaves into HBM bitmaps first
 // (invexp_kernel: one write and one read of a doc bitmap per leaf), a workgroup takes one (segment, 65,536-doc
 // container key) unit at a time, ORs the key's container of each leaf's ids into an 8 KiB LDS image per leaf
@@ -3998,7 +3998,7 @@ __global__ __launch_bounds__(PGPU_DIRECT_THREADS) void query_kernel_rkey(DevPara
 }
 
 // ================================================================================================================
-// CANDIDATE ITERATION from a sparse leading index leaf (p.direct == 6).  AndDocIdSet.iterator iterates the index
+// CANDIDATE ITERATION from a sparse leading index leaf (p.direct == PGPU_KV_CAND).  AndDocIdSet.iterator iterates the index
 // child's bitmap and applies the scan children to those docs only (AndDocIdSet.java:87-140, SVScanDocIdIterator
 // .applyAnd :79-94).  When every segment's dense program is one inclusive inverted or sorted leaf holding few docs,
 // the launch runs over that leaf's Roaring containers (or sorted doc ranges split at 65,536-doc keys) -- one unit
@@ -5725,7 +5725,7 @@ static hipError_t rk_attr(size_t lds_bytes) {
 // columns of <= 20 planes keep three waves per SIMD, of 24 two)
 [[maybe_unused]] static void rp_launch(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st) {
   const dim3 g(grid), b(PGPU_DIRECT_THREADS);
-  if (p.direct == 5) {  // the inverted leaves' containers read into LDS per unit (query_kernel_rkey)
+  if (p.direct == PGPU_KV_RKEY) {  // the inverted leaves' containers read into LDS per unit (query_kernel_rkey)
     const dim3 kb(PGPU_DIRECT_THREADS);
     if (p.rk_ids) {  // the aggregated columns' packed 16-bit ids, values gathered for the matched docs
       if (p.rd_planes <= 1) hipLaunchKernelGGL((query_kernel_rkey<1, 16, true>), g, kb, dyn_smem, st, p);
@@ -5781,21 +5781,21 @@ template <int M>
   }                                                                                                             \
   hipError_t pgpu_launch_direct_##NAME(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st,          \
                                        hipEvent_t ev0, hipEvent_t ev1) {                                        \
-    if (p.direct == 6) {                                                                                        \
+    if (p.direct == PGPU_KV_CAND) {                                                                             \
       if constexpr (M != PGPU_MODE_PART)                                                                        \
         hipLaunchKernelGGL((query_kernel_cand<M>), dim3(grid), dim3(PGPU_DIRECT_THREADS), dyn_smem, st, p);     \
       else                                                                                                      \
         return hipErrorInvalidValue;                                                                            \
-    } else if (p.direct == 8) {                                                                                 \
+    } else if (p.direct == PGPU_KV_RFSM) {                                                                      \
       if constexpr (M != PGPU_MODE_PART) rf_launch<M>(p, grid, dyn_smem, st);                                   \
       else return hipErrorInvalidValue;                                                                         \
-    } else if (p.direct >= 3) {                                                                                 \
+    } else if (p.direct == PGPU_KV_RSTREAM || p.direct == PGPU_KV_RPROG || p.direct == PGPU_KV_RKEY) {          \
       if constexpr (M == PGPU_MODE_AGG) {                                                                       \
-        if (p.direct == 3) rs_launch(p, grid, dyn_smem, st);                                                    \
+        if (p.direct == PGPU_KV_RSTREAM) rs_launch(p, grid, dyn_smem, st);                                      \
         else rp_launch(p, grid, dyn_smem, st);                                                                  \
       } else                                                                                                    \
         return hipErrorInvalidValue;                                                                            \
-    } else if (p.direct == 2) {                                                                                 \
+    } else if (p.direct == PGPU_KV_RDIRECT) {                                                                   \
       if (p.rd_pfx) rd_launch<M, PGPU_PFX_PLANES>(p, grid, dyn_smem, st, ev0, ev1);                             \
       else rd_launch<M, 0>(p, grid, dyn_smem, st, ev0, ev1);                                                    \
     } else                                                                                                      \
@@ -6264,7 +6264,7 @@ hipError_t pgpu_launch_leafbits(const DevParams& p, hipStream_t st) {
 
 hipError_t pgpu_launch_andfsm(const DevParams& p, bool s2, uint32_t* fn, int64_t* out, hipStream_t st) {
   if (p.nseg <= 0) return hipSuccess;
-  if (p.total_tiles > 0 && p.direct != 8) {  // (query_kernel_rfsm has written the tile maps)  // ~8 workgroups per CU, each wave over a contiguous run of tiles
+  if (p.total_tiles > 0 && p.direct != PGPU_KV_RFSM) {  // (query_kernel_rfsm has written the tile maps)  // ~8 workgroups per CU, each wave over a contiguous run of tiles
     const dim3 g(std::min(2048, (p.total_tiles + 3) / 4));
     if (s2) hipLaunchKernelGGL(andfsm_tile_kernel<true>, g, dim3(256), 0, st, p, fn);
     else hipLaunchKernelGGL(andfsm_tile_kernel<false>, g, dim3(256), 0, st, p, fn);

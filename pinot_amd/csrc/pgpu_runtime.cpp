@@ -91,6 +91,19 @@ int fail(int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(PGPU_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
+// Environment switches: on when set to a non-zero integer.  Most are read once per process (a static const where
+// they are used); the ones tests flip within one process are read per plan, and say so.
+bool env_flag(const char* name) {
+  const char* v = getenv(name);
+  return v && atoi(v) != 0;
+}
+int env_int(const char* name) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : 0;
+}
+
+size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
 inline uint32_t be32(const uint8_t* p) {
   return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
 }
@@ -1120,7 +1133,7 @@ bool reserve_derived(pgpu_context* ctx, uint64_t bytes) {
 }
 
 int seal_column(pgpu_segment* seg, size_t i) {
-  static const bool no_slice = getenv("PGPU_NO_SLICE") && atoi(getenv("PGPU_NO_SLICE")) != 0;
+  static const bool no_slice = env_flag("PGPU_NO_SLICE");
   HostColumn& c = seg->cols[i];
   // derived copies (PhysicalColumnIndexContainer.java:80,151-156 loads only the indexes IndexLoadingConfig names):
   // the column's pgpu_segment_set_derived flags, within the context's budget; the kernels plan without them
@@ -1138,7 +1151,7 @@ int seal_column(pgpu_segment* seg, size_t i) {
   }
   // value planes (bit-sliced index of the values): SUM is then sum_k 2^k popcount(plane_k & matched) per tile and
   // MIN / MAX an MSB-first selection -- no per-doc id extraction, no dictionary gather (PGPU_AM_SLICED)
-  static const bool no_vslice = getenv("PGPU_NO_VSLICE") && atoi(getenv("PGPU_NO_VSLICE")) != 0;
+  static const bool no_vslice = env_flag("PGPU_NO_VSLICE");
   if (c.kind == PGPU_COL_FIXED_BIT && !no_vslice && !c.vsliced.p && c.dict.p && c.dict_card > 0 &&
       (c.dict_type == PGPU_INT || c.dict_type == PGPU_LONG) && c.hdict.size() >= (size_t)c.dict_card * type_width(c.dict_type)) {
     int64_t lo, hi;
@@ -1467,7 +1480,7 @@ int pgpu_table_layout_of(const pgpu_query_desc* q, pgpu_table_layout* out) {
   // FLOAT / DOUBLE SUM / AVG in fixed point (fx_parts[a] 21-bit part sections each, pgpu_fixed_sum_layout) when the
   // column is finite and the part count fits; otherwise that aggregation keeps a float64 section (and all of them do
   // when the part sections would not fit the table).  PGPU_NO_FIXED_SUM=1 forces float64.
-  static const bool no_fixed = getenv("PGPU_NO_FIXED_SUM") && atoi(getenv("PGPU_NO_FIXED_SUM")) != 0;
+  static const bool no_fixed = env_flag("PGPU_NO_FIXED_SUM");
   if (q->sum_exp && !q->sum_parts) return fail(PGPU_E_INVALID, "sum_exp without sum_parts");
   int32_t fx_exp[16], fx_parts[16];
   bool fixed_all = !no_fixed;
@@ -1943,7 +1956,7 @@ int convert_filter(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const 
         if (!c->inv_dir) return fail(PGPU_E_INVALID, "INVERTED on column %d without inverted index", nd.column);
         for (int k = 0; k < nd.num_ids; ++k)
           if (nd.ids[k] < 0 || nd.ids[k] >= c->card) return fail(PGPU_E_INVALID, "bitmap id %d out of range", nd.ids[k]);
-        static const bool no_invexp = getenv("PGPU_NO_INVEXP") && atoi(getenv("PGPU_NO_INVEXP")) != 0;
+        static const bool no_invexp = env_flag("PGPU_NO_INVEXP");
         if (!no_invexp && nd.num_ids > 0) {
           const int64_t woff = inv_leaf(pk, seg, *c, nd);
           if (woff >= 0) {  // the expanded bitmap as a BITS leaf (a bitmap leaf reads no entries)
@@ -2188,7 +2201,7 @@ void plan_prefix(const SegView& v, const Packer& pk, double rho_dense, DevSeg& d
   ds.pfx_col = -1;
   ds.pfx_nr = 0;
   for (int r = 0; r < PGPU_SLICE_RANGES; ++r) ds.pfx_rng[r][0] = ds.pfx_rng[r][1] = 0;
-  static const bool no_pfx = getenv("PGPU_NO_PREFIX") && atoi(getenv("PGPU_NO_PREFIX")) != 0;
+  static const bool no_pfx = env_flag("PGPU_NO_PREFIX");
   if (no_pfx || ds.rprog_len != 1) return;
   const DevInstr& in = pk.instrs[ds.rprog_begin];
   if (in.op != PGPU_I_SCAN || in.kind != PGPU_COL_FIXED_BIT || in.negate || in.nostat) return;
@@ -2288,7 +2301,7 @@ int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pg
   for (int a = 0; a < q->num_aggs; ++a)
     if (q->aggs[a].fn != PGPU_AGG_COUNT) add_agg(q->aggs[a].column);
   int agg_mode;
-  static const bool no_sliced = getenv("PGPU_NO_SLICED_AGG") && atoi(getenv("PGPU_NO_SLICED_AGG")) != 0;
+  static const bool no_sliced = env_flag("PGPU_NO_SLICED_AGG");
   static const double sliced_touch = getenv("PGPU_SLICED_TOUCH") ? atof(getenv("PGPU_SLICED_TOUCH")) : kSlicedAggTouch;
   // (aggregation-only: p.mode is still undecided for dense group-by tables here)
   // every aggregation answered from value planes (SUM of whole int64 cells, MIN, MAX over an INT / LONG dictionary
@@ -2490,7 +2503,7 @@ int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pg
   // kernel's counted vmcnt then covers them too, where a plain load behind the DMAs waits for every DMA in flight.
   // Measured slower (config 2: 2.52 against 1.14 ms; config 3's query kernel 2.44 against 0.93 ms): the wider
   // slots cut the resident workgroups and the DMA depth more than the in-order waits cost, so it is opt-in.
-  static const bool vstage = getenv("PGPU_VSTAGE") && atoi(getenv("PGPU_VSTAGE")) != 0;
+  static const bool vstage = env_flag("PGPU_VSTAGE");
   ds.nvstage = 0;
   if (agg_mode == PGPU_AM_SLICED && all_bsi && vstage) {
     std::vector<int> vcols;
@@ -2770,7 +2783,7 @@ int pack_query(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_lay
   p.total_tiles = (int32_t)tiles;
   p.max_instrs = pk.max_instrs;
   if (q->flags & PGPU_Q_EXACT_FILTER_STATS) {
-    static const bool no_fsm = getenv("PGPU_NO_ANDFSM") && atoi(getenv("PGPU_NO_ANDFSM")) != 0;
+    static const bool no_fsm = env_flag("PGPU_NO_ANDFSM");
     bool fsm = !no_fsm;
     for (int s = 0; s < q->num_segments && fsm; ++s) {
       const int k = pk.segs[s].leaf_len;
@@ -2798,65 +2811,81 @@ int pack_query(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_lay
   return PGPU_OK;
 }
 
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+// ---- launch phases (launch_impl) ------------------------------------------------------------------------------
+// replay drop -> plan_launch (no HIP call) -> workspace buffers -> arena -> enqueue (fused or split) -> handle
 
-}  // namespace
+// What plan_launch decides beyond the fields of DevParams the kernels read
+struct LaunchPlan {
+  int grid = 1;
+  size_t dyn = 0;  // dynamic LDS bytes of the query kernel
+  int nwaves = 0;  // rows of the per-wave slab and statistics
+  // PGPU_MODE_PART record geometry (copied into DevParams by ensure_part_records)
+  int pcol = -1;   // query column carried in the records (-1: COUNT only)
+  int pshift = 0;  // keys per partition = 1 << pshift
+  uint64_t nparts = 0;
+  int part_idbits = 0;  // > 0: one-word records (DevParams::rec_idbits)
+  const void* part_pdict = nullptr;
+  int part_rw = 1;
+  int slice_shift = 0, ldict = 0;
+  uint32_t pdict_n = 0;
+  const HostColumn* for_h = nullptr;  // ldict 2: the column whose frame-of-reference image phase 2 reads
+};
 
-extern "C" {
+// PGPU_DIRECT_WGS: workgroups per CU of the self-loading kernels (0: the variant's own choice)
+int env_direct_wgs() {
+  static const int wgs = env_int("PGPU_DIRECT_WGS");
+  return wgs;
+}
 
-// host_table (device-visible pointer into pinned host memory, or null): the finished table is also exported there
-namespace {
-int enqueue_compact(pgpu_context* ctx, Workspace* ws, const pgpu_table_layout* L, const void* dev_table,
-                    hipStream_t st, const pgpu_topk* order);
-}  // namespace
+// Grid of a self-loading kernel: per_cu workgroups per CU, at most one per `per_wg` tiles (or units), rounded down
+// to a multiple of 8 once there are 8
+int stream_grid(int num_cus, int per_cu, int work, int per_wg) {
+  int g = (int)std::min<int64_t>((int64_t)num_cus * per_cu, std::max(1, work / per_wg));
+  if (g >= 8) g &= ~7;
+  return std::max(1, g);
+}
 
-// eager: compact the table (only the best groups by eager_order, when given) on the query's stream right behind
-// its kernels, into the workspace; pgpu_query_collect then only copies the rows out (pgpu_query_submit_ordered)
-// tws (pgpu_query_submit*): the workspace owning dev_table (its `table`); with it a register-direct query with a small
-// table runs as one launch (see Workspace::ticket) and may take the workspace's spare table as its table
-static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream, void* dev_table,
-                       uint64_t table_bytes, int64_t* host_table, pgpu_query** out_query, bool eager = false,
-                       const pgpu_topk* eager_order = nullptr, Workspace* tws = nullptr) {
-  if (!ctx || !q || !out_query) return fail(PGPU_E_INVALID, "null argument");
-  pgpu_table_layout L;
-  int rc = pgpu_table_layout_of(q, &L);
-  if (rc) return rc;
-  const uint64_t need = pgpu_table_bytes(&L);
-  if (!dev_table || table_bytes < need)
-    return fail(PGPU_E_INVALID, "table buffer %llu bytes < %llu needed", (unsigned long long)table_bytes,
-                (unsigned long long)need);
-  Packer pk;
-  DevParams p;
-  const double tp0 = HostTiming::us();
-  rc = pack_query(ctx, q, L, pk, p);
-  host_timing().add(2, tp0, HostTiming::us());
-  if (rc) return rc;
-  if (pk.leaf_words > 0 && !pk.legacy_range) {
-    // the reference's numEntriesScannedInFilter requested, but every segment's program is one whose GPU count IS
-    // the reference's (scans driven by next(): OR / NOT trees, index merges then applyAnd, a lone multi-value scan;
-    // pgpu_filter_count_is_reference): no leaf bitmaps, no copy to the host, no replay
-    bool all_ref = true;
-    for (int s = 0; s < q->num_segments && all_ref; ++s) {
-      const pgpu_segment_plan& sp = q->segments[s];
-      all_ref = pgpu_filter_count_is_reference(sp.filter, sp.num_filter_nodes);
-      int nmv = 0;
-      for (int i = 0; i < sp.num_filter_nodes && all_ref; ++i) {
-        const pgpu_filter_node& nd = sp.filter[i];
-        if (nd.op != PGPU_F_SCAN || nd.column < 0 || nd.column >= q->num_columns) continue;
-        const int32_t slot = sp.column_map[nd.column];
-        nmv += slot >= 0 && slot < (int32_t)sp.segment->cols.size() && sp.segment->cols[slot].kind == PGPU_COL_MV;
-      }
-      all_ref = all_ref && (nmv == 0 || sp.num_filter_nodes == 1);
-    }
-    const bool always_replay = getenv("PGPU_ALWAYS_REPLAY") && atoi(getenv("PGPU_ALWAYS_REPLAY")) != 0;  // (per plan: tests)
-    if (all_ref && !always_replay) {
-      pk.leaf_words = 0;
-      for (DevSeg& ds : pk.segs) ds.leaf_len = 0;
-    }
+// Dynamic LDS of the register kernels (rdirect, rstream, rprog, rfsm; rkey adds its buffers): four waves' consumer
+// areas, the LDS table, 16 bytes of workgroup state
+size_t reg_kernel_lds(const DevParams& p) { return (size_t)4 * p.cons_bytes + align16(p.ltab_bytes) + 16; }
+
+// An aggregation the register-streaming kernels answer from a column's value planes
+bool value_plane_agg(const DevAgg& ag) {
+  return (ag.op == PGPU_RED_SUM_I64 && ag.part == 0) || ag.op == PGPU_RED_MIN_I64 || ag.op == PGPU_RED_MAX_I64;
+}
+
+// The multi-value column a SCAN node reads, or null (another node, a single-value column)
+const HostColumn* mv_scan_column(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pgpu_filter_node& nd) {
+  if (nd.op != PGPU_F_SCAN || nd.column < 0 || nd.column >= q->num_columns) return nullptr;
+  const int32_t slot = sp.column_map[nd.column];
+  if (slot < 0 || slot >= (int32_t)sp.segment->cols.size()) return nullptr;
+  const HostColumn* hc = &sp.segment->cols[slot];
+  return hc->kind == PGPU_COL_MV ? hc : nullptr;
+}
+
+// The reference's numEntriesScannedInFilter requested, but every segment's program is one whose GPU count IS the
+// reference's (scans driven by next(): OR / NOT trees, index merges then applyAnd, a lone multi-value scan;
+// pgpu_filter_count_is_reference): no leaf bitmaps, no copy to the host, no replay
+void drop_reference_replay(const pgpu_query_desc* q, Packer& pk) {
+  if (pk.leaf_words <= 0 || pk.legacy_range) return;
+  bool all_ref = true;
+  for (int s = 0; s < q->num_segments && all_ref; ++s) {
+    const pgpu_segment_plan& sp = q->segments[s];
+    all_ref = pgpu_filter_count_is_reference(sp.filter, sp.num_filter_nodes);
+    int nmv = 0;
+    for (int i = 0; i < sp.num_filter_nodes && all_ref; ++i) nmv += mv_scan_column(q, sp, sp.filter[i]) != nullptr;
+    all_ref = all_ref && (nmv == 0 || sp.num_filter_nodes == 1);
   }
-  HIP_TRY(hipSetDevice(ctx->device));
+  if (all_ref && !env_flag("PGPU_ALWAYS_REPLAY")) {  // (per plan: tests)
+    pk.leaf_words = 0;
+    for (DevSeg& ds : pk.segs) ds.leaf_len = 0;
+  }
+}
 
-  // mode and LDS geometry: consumer areas, optional LDS group table, then as many ring slots as fit
+// Mode and the ring kernel's LDS geometry: consumer areas, optional LDS group table, then as many ring slots as
+// fit.  Every later decision starts from this plan (PGPU_KV_RING).
+int plan_mode_and_ring(int num_cus, const pgpu_query_desc* q, const pgpu_table_layout& L, const Packer& pk,
+                       DevParams& p, LaunchPlan& pl) {
   const uint64_t tbytes = 8ull * L.num_sections * L.num_keys;
   const int S = (int)align16(std::max(16, pk.slot_bytes));
   bool any_dense = false;
@@ -2870,26 +2899,26 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
   const size_t fixed = pgpu_lds_fixed_bytes(p.dense, 0, p.mask_rows);
   // LDS-privatised table only when it fits next to >= 4 ring slots and enough docs are expected to match to pay
   // for initialising and flushing one table copy per workgroup
-  int grid = std::max(1, std::min(ctx->num_cus, p.total_tiles));
-  const bool many = pk.est_matched > 4.0 * (double)L.num_keys * grid;
+  pl.grid = std::max(1, std::min(num_cus, p.total_tiles));
+  const bool many = pk.est_matched > 4.0 * (double)L.num_keys * pl.grid;
   // partitioned group-by (PGPU_MODE_PART): large key spaces, at most one aggregated column of a 4-byte type
   bool part_ok = q->num_group_columns > 0 &&
                  (L.num_keys >= PGPU_PART_MIN_KEYS || (q->flags & PGPU_Q_PARTITION) != 0);
-  int pcol = -1;
+  pl.pcol = -1;
   for (int a = 0; a < p.nagg && part_ok; ++a) {
     if (p.aggs[a].fn == PGPU_AGG_COUNT) continue;
-    if (pcol >= 0 && p.aggs[a].col != pcol) part_ok = false;
+    if (pl.pcol >= 0 && p.aggs[a].col != pl.pcol) part_ok = false;
     if (p.aggs[a].vtype != PGPU_INT && p.aggs[a].vtype != PGPU_FLOAT) part_ok = false;
     if (p.aggs[a].part != 0) part_ok = false;  // records carry whole 4-byte values
-    if (pcol < 0) {
-      pcol = p.aggs[a].col;
+    if (pl.pcol < 0) {
+      pl.pcol = p.aggs[a].col;
       p.aggs[a].emit = 1;
     }
   }
-  int pshift = 0;
-  while ((8ull * L.num_sections << (pshift + 1)) <= PGPU_PART_LDS_BYTES) ++pshift;
-  uint64_t nparts = (L.num_keys + (1ull << pshift) - 1) >> pshift;
-  part_ok = part_ok && nparts <= PGPU_PART_MAX_PARTS && L.num_keys < (1ull << 31) &&
+  pl.pshift = 0;
+  while ((8ull * L.num_sections << (pl.pshift + 1)) <= PGPU_PART_LDS_BYTES) ++pl.pshift;
+  pl.nparts = (L.num_keys + (1ull << pl.pshift) - 1) >> pl.pshift;
+  part_ok = part_ok && pl.nparts <= PGPU_PART_MAX_PARTS && L.num_keys < (1ull << 31) &&
             L.num_sections <= PGPU_PART_MAX_SECTIONS && !p.mv_gmask;  // one record per doc: no value expansion
   if (q->num_group_columns == 0) p.mode = PGPU_MODE_AGG;
   else if (L.key_kind == PGPU_KEYS_HASH) p.mode = PGPU_MODE_HASH;
@@ -2900,7 +2929,7 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
   else p.mode = PGPU_MODE_GLOBAL;
   if (p.mode != PGPU_MODE_PART)
     for (int a = 0; a < p.nagg; ++a) p.aggs[a].emit = 0;
-  p.ltab_bytes = p.mode == PGPU_MODE_LDS ? (int32_t)tbytes : (p.mode == PGPU_MODE_PART ? (int32_t)(4 * nparts) : 0);
+  p.ltab_bytes = p.mode == PGPU_MODE_LDS ? (int32_t)tbytes : (p.mode == PGPU_MODE_PART ? (int32_t)(4 * pl.nparts) : 0);
   const size_t avail = PGPU_LDS_LIMIT - fixed - align16(p.ltab_bytes);
   p.slot_bytes = S;
   p.ring_slots = (int32_t)std::min<size_t>(PGPU_RING_MAX, avail / S);
@@ -2917,442 +2946,466 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
     const int64_t by_bytes = (64 * 1024 + nload * pk.tile_bytes - 1) / (nload * pk.tile_bytes);
     p.inflight = (int32_t)std::max<int64_t>(1, std::min(by_ring, by_bytes));
   }
-  size_t dyn = pgpu_lds_bytes(p.dense, p.ring_slots, S, p.ltab_bytes, p.mask_rows);
-  // direct (self-loading) variant: every segment's staged columns are its bit-sliced fast leaves and no segment
-  // aggregates densely; each wave streams its own tiles through two private LDS slots (query_kernel_direct)
-  static const bool no_direct = getenv("PGPU_NO_DIRECT") && atoi(getenv("PGPU_NO_DIRECT")) != 0;
-  p.direct = 0;
-  // a segment whose dense program reads no staged column (bitmap / sorted / precomputed-bitmap leaves only) also runs
-  // on self-loading waves, interpreting its program without slots: the ring's few consumer waves cannot hide the
-  // candidate gathers' latency
+  p.direct = PGPU_KV_RING;
+  pl.dyn = pgpu_lds_bytes(p.dense, p.ring_slots, S, p.ltab_bytes, p.mask_rows);
+  return PGPU_OK;
+}
+
+// A staged segment whose staged columns are exactly its bit-sliced fast leaves, or one that stages nothing
+bool sliced_leaves_only(const DevSeg& ds) {
+  return (ds.fast >= 1 && ds.nstage == ds.fast && ds.stage_sliced == (1 << ds.nstage) - 1) ||
+         (ds.nstage == 0 && ds.fast == 0);
+}
+
+// The self-loading kernels (direct, rdirect, rstream) apply: no segment aggregates densely or by partition, every
+// segment's staged columns are its bit-sliced fast leaves -- or its dense program reads no staged column at all
+// (bitmap / sorted / precomputed-bitmap leaves only), which also runs on self-loading waves, interpreting its
+// program without slots: the ring's few consumer waves cannot hide the candidate gathers' latency
+bool self_loading_ok(const Packer& pk, const DevParams& p) {
+  static const bool no_direct = env_flag("PGPU_NO_DIRECT");
   bool index_only = true;
   for (const DevSeg& ds : pk.segs) index_only &= ds.ntiles == 0 || (ds.nstage == 0 && ds.fast == 0);
   // (multi-value group keys expand per candidate in the ring kernel only: sparse_agg<MODE, MV>)
-  if (!no_direct && !p.dense && p.mode != PGPU_MODE_PART && !p.mv_gmask && (pk.tile_bytes > 0 || index_only)) {
-    bool ok = true;
-    for (const DevSeg& ds : pk.segs)
-      ok &= ds.ntiles == 0 || ((ds.agg_mode == PGPU_AM_COUNT || ds.agg_mode == PGPU_AM_SPARSE) &&
-                               ((ds.fast >= 1 && ds.nstage == ds.fast && ds.stage_sliced == (1 << ds.nstage) - 1) ||
-                                (ds.nstage == 0 && ds.fast == 0))) ||
-            (ds.agg_mode == PGPU_AM_SLICED &&
-             ((ds.fast >= 1 && ds.nstage == ds.fast && ds.stage_sliced == (1 << ds.nstage) - 1) ||
-              (ds.nstage == 0 && ds.fast == 0)));
-    // up to five 4-wave workgroups per CU (more waves hide the per-tile latency better than deeper prefetch, which
-    // measured flat); each wave keeps D - 1 tiles in flight, aiming at ~12 KiB (HBM latency
-    // x per-CU bandwidth), within the 6-bit vmcnt and the LDS
-    int max_instrs = 1, min_instrs = 64;
-    for (const DevSeg& ds : pk.segs)
-      if (ds.ntiles) {
-        max_instrs = std::max(max_instrs, ds.stage_instrs);
-        min_instrs = std::min(min_instrs, ds.stage_instrs);
-      }
-    int D = (int)std::max<int64_t>(2, std::min<int64_t>(8, 1 + (12 * 1024 + pk.tile_bytes - 1) / std::max<int64_t>(1, pk.tile_bytes)));
-    D = std::min(D, 1 + 63 / max_instrs);
-    static const int env_slots = getenv("PGPU_DIRECT_SLOTS") ? atoi(getenv("PGPU_DIRECT_SLOTS")) : 0;
-    static const int env_wgs = getenv("PGPU_DIRECT_WGS") ? atoi(getenv("PGPU_DIRECT_WGS")) : 0;  // per CU
-    if (env_slots >= 2) D = std::min(env_slots, 1 + 63 / max_instrs);
-    // as many 4-wave workgroups as LDS and VGPRs allow: 5 (20 waves) where the kernel fits 96 VGPRs
-    // (PGPU_DIRECT_MIN_WAVES), else 4 -- a fifth workgroup that cannot be resident only adds a tail
-    const int wgs = env_wgs >= 1 ? env_wgs : ((p.mode == PGPU_MODE_GLOBAL || p.mode == PGPU_MODE_HASH) ? 5 : 4);
-    auto ddyn_of = [&](int d) { return (size_t)4 * p.cons_bytes + align16(p.ltab_bytes) + (size_t)4 * d * S; };
-    while (D > 2 && wgs * ddyn_of(D) > PGPU_LDS_LIMIT) --D;
-    const size_t ddyn = ddyn_of(D);
-    if (ok && D >= 2 && ddyn <= PGPU_LDS_LIMIT) {
-      const int per_cu = (int)std::min<size_t>(wgs, PGPU_LDS_LIMIT / ddyn);
-      int g = std::min<int64_t>((int64_t)ctx->num_cus * per_cu, std::max(1, p.total_tiles / 16));
-      if (g >= 8) g &= ~7;
-      p.direct = 1;
-      p.dslots = D;
-      p.min_instrs = std::max(1, min_instrs);
-      grid = std::max(1, g);
-      dyn = ddyn;
+  if (no_direct || p.dense || p.mode == PGPU_MODE_PART || p.mv_gmask || !(pk.tile_bytes > 0 || index_only))
+    return false;
+  bool ok = true;
+  for (const DevSeg& ds : pk.segs)
+    ok &= ds.ntiles == 0 ||
+          ((ds.agg_mode == PGPU_AM_COUNT || ds.agg_mode == PGPU_AM_SPARSE || ds.agg_mode == PGPU_AM_SLICED) &&
+           sliced_leaves_only(ds));
+  return ok;
+}
+
+// direct (query_kernel_direct): each wave streams its own tiles through private LDS slots
+void try_direct(int num_cus, const Packer& pk, DevParams& p, LaunchPlan& pl) {
+  // up to five 4-wave workgroups per CU (more waves hide the per-tile latency better than deeper prefetch, which
+  // measured flat); each wave keeps D - 1 tiles in flight, aiming at ~12 KiB (HBM latency
+  // x per-CU bandwidth), within the 6-bit vmcnt and the LDS
+  int max_instrs = 1, min_instrs = 64;
+  for (const DevSeg& ds : pk.segs)
+    if (ds.ntiles) {
+      max_instrs = std::max(max_instrs, ds.stage_instrs);
+      min_instrs = std::min(min_instrs, ds.stage_instrs);
     }
-    // register-direct (query_kernel_rdirect): one bit-sliced fast leaf of <= 16 bits per segment is the only staged
-    // column -- its planes stream into VGPRs, no LDS slots (tools/stream_bench.hip: 5.6-6.0 TB/s)
-    static const bool no_rdirect = getenv("PGPU_NO_RDIRECT") && atoi(getenv("PGPU_NO_RDIRECT")) != 0;
-    bool rd = ok && !no_rdirect;
-    int rd_bits = 1;
-    for (const DevSeg& ds : pk.segs)
-      if (ds.ntiles) {
-        if (!(ds.nstage == 1 && ds.fast == 1 && ds.stage_sliced == 1) || ds.agg_mode == PGPU_AM_SLICED) {
-          rd = false;
-          continue;
-        }
-        const DevColumn& c = pk.cols[ds.col_begin + ds.stage_col[0]];
-        rd &= c.bits >= 1 && c.bits <= 16;
-        rd_bits = std::max(rd_bits, (int)c.bits);
-      }
-    const size_t rdyn = (size_t)4 * p.cons_bytes + align16(p.ltab_bytes) + 16;
-    if (rd && rdyn <= PGPU_LDS_LIMIT) {
-      // 104-126 VGPRs (4 waves per SIMD) except the aggregation-only mode (136-152: 3)
-      const int per_cu = (int)std::min<size_t>(env_wgs >= 1 ? env_wgs : (p.mode == PGPU_MODE_AGG ? 3 : 4),
-                                               PGPU_LDS_LIMIT / rdyn);
-      int g = std::min<int64_t>((int64_t)ctx->num_cus * per_cu, std::max(1, p.total_tiles / 16));
-      if (g >= 8) g &= ~7;
-      p.direct = 2;
-      p.rd_planes = rd_bits <= 8 ? 8 : rd_bits <= 10 ? 10 : rd_bits <= 12 ? 12 : 16;
-      // prefix pre-filter when every segment's residual leaf has one (plan_prefix)
-      bool pfx = true;
-      for (const DevSeg& ds : pk.segs) pfx &= ds.ntiles == 0 || ds.pfx_col >= 0;
-      p.rd_pfx = pfx && p.rd_planes <= 12 ? PGPU_PFX_PLANES : 0;  // (no 16 + 3-plane variant: > 128 VGPRs)
-      p.dslots = 0;
-      grid = std::max(1, g);
-      dyn = rdyn;
-    }
-    // register streaming (query_kernel_rstream): aggregation-only, every segment an AND of two bit-sliced fast
-    // leaves (<= 16 and <= 8 bits) with its aggregations all answered from one column's value planes (<= 24)
-    const bool no_rstream = getenv("PGPU_NO_RSTREAM") && atoi(getenv("PGPU_NO_RSTREAM")) != 0;  // per plan (tests)
-    bool rs = ok && !no_rstream && p.mode == PGPU_MODE_AGG && rdyn <= PGPU_LDS_LIMIT;
-    int vcol = -1, rs_narrow = 1, rs_vb = 1;
-    for (int a = 0; a < p.nagg && rs; ++a) {
-      const DevAgg& ag = p.aggs[a];
-      if (ag.fn == PGPU_AGG_COUNT) continue;
-      rs = (vcol < 0 || vcol == ag.col) && ((ag.op == PGPU_RED_SUM_I64 && ag.part == 0) ||
-                                            ag.op == PGPU_RED_MIN_I64 || ag.op == PGPU_RED_MAX_I64);
-      vcol = ag.col;
-    }
-    rs = rs && vcol >= 0;
-    for (const DevSeg& ds : pk.segs) {
-      if (!rs || !ds.ntiles) continue;
-      rs = ds.nstage == 2 && ds.fast == 2 && ds.stage_sliced == 3 && ds.agg_mode == PGPU_AM_SLICED &&
-           ds.rprog_len == 0 && ds.f_nr[0] > 0 && ds.f_nr[1] > 0;
-      if (!rs) break;
-      const DevColumn& vc = pk.cols[ds.col_begin + vcol];
-      int b[2];
-      for (int j = 0; j < 2; ++j) b[j] = pk.cols[ds.col_begin + pk.instrs[ds.prog_begin + ds.fast_ins[j]].col].bits;
-      rs = vc.vsliced && vc.vbits >= 1 && vc.vbits <= 24 && std::max(b[0], b[1]) <= 16 && std::min(b[0], b[1]) >= 1 &&
-           std::min(b[0], b[1]) <= 8;
-      rs_narrow = std::max(rs_narrow, std::min(b[0], b[1]));
-      rs_vb = std::max(rs_vb, (int)vc.vbits);
-    }
-    if (rs) {
-      const int per_cu = (int)std::min<size_t>(env_wgs >= 1 ? env_wgs : 3, PGPU_LDS_LIMIT / rdyn);
-      int g = std::min<int64_t>((int64_t)ctx->num_cus * per_cu, std::max(1, p.total_tiles / 16));
-      if (g >= 8) g &= ~7;
-      p.direct = 3;
-      p.rd_planes = rs_narrow <= 4 ? 4 : 8;
-      p.rs_vplanes = rs_vb <= 16 ? 16 : 24;
-      p.rd_pfx = 0;
-      p.dslots = 0;
-      grid = std::max(1, g);
-      dyn = rdyn;
-    }
-  }
-  // register streaming of index-only programs (query_kernel_rprog): aggregation-only, every segment's dense program
-  // a truth table over <= 5 bitmap / sorted leaves, its aggregations from <= 2 columns' value planes (<= 24)
-  if (p.direct == 1 && p.mode == PGPU_MODE_AGG) {
-    const bool no_rprog = getenv("PGPU_NO_RPROG") && atoi(getenv("PGPU_NO_RPROG")) != 0;  // per plan (tests)
-    bool rp = !no_rprog;
-    int vcols[2] = {-1, -1}, nv = 0, vbmax = 1;
-    for (int a = 0; a < p.nagg && rp; ++a) {
-      const DevAgg& ag = p.aggs[a];
-      if (ag.fn == PGPU_AGG_COUNT || ag.col == vcols[0] || ag.col == vcols[1]) continue;
-      rp = nv < 2 && ((ag.op == PGPU_RED_SUM_I64 && ag.part == 0) || ag.op == PGPU_RED_MIN_I64 ||
-                      ag.op == PGPU_RED_MAX_I64);
-      if (rp) vcols[nv++] = ag.col;
-    }
-    for (int a = 0; a < p.nagg && rp; ++a)  // (every aggregation over a value column must be a value-plane one)
-      if (p.aggs[a].fn != PGPU_AGG_COUNT)
-        rp = (p.aggs[a].op == PGPU_RED_SUM_I64 && p.aggs[a].part == 0) || p.aggs[a].op == PGPU_RED_MIN_I64 ||
-             p.aggs[a].op == PGPU_RED_MAX_I64;
-    rp = rp && nv >= 1;
-    for (DevSeg& ds : pk.segs) {
-      if (!rp || !ds.ntiles) continue;
-      rp = ds.nstage == 0 && ds.fast == 0 && ds.agg_mode == PGPU_AM_SLICED && ds.rprog_len == 0 && ds.nvstage == 0 &&
-           program_truth_table(pk, ds);
-      for (int c = 0; c < nv && rp; ++c) {
-        const DevColumn& vc = pk.cols[ds.col_begin + vcols[c]];
-        rp = vc.vsliced && vc.vbits >= 1 && vc.vbits <= 24;
-        vbmax = std::max(vbmax, (int)vc.vbits);
-      }
-    }
-    const size_t rdyn = (size_t)4 * p.cons_bytes + align16(p.ltab_bytes) + 16;
-    if (rp && rdyn <= PGPU_LDS_LIMIT) {
-      static const int env_wgs = getenv("PGPU_DIRECT_WGS") ? atoi(getenv("PGPU_DIRECT_WGS")) : 0;  // per CU
-      const int per_cu = (int)std::min<size_t>(env_wgs >= 1 ? env_wgs : (nv > 1 && vbmax > 20 ? 2 : 3),
-                                               PGPU_LDS_LIMIT / rdyn);
-      int g = std::min<int64_t>((int64_t)ctx->num_cus * per_cu, std::max(1, p.total_tiles / 16));
-      if (g >= 8) g &= ~7;
-      p.direct = 4;
-      p.rd_planes = nv;
-      p.rs_vplanes = vbmax <= 16 ? 16 : (vbmax <= 20 && nv > 1) ? 20 : 24;
-      p.rd_pfx = 0;
-      p.dslots = 0;
-      grid = std::max(1, g);
-      dyn = rdyn;
-      // every BITS leaf an inverted one: read the containers per (segment, container key) unit into LDS instead of
-      // expanding them into HBM bitmaps first (query_kernel_rkey)
-      const bool no_rkey = getenv("PGPU_NO_RKEY") && atoi(getenv("PGPU_NO_RKEY")) != 0;  // per plan (tests)
-      // (not under the exact-statistics replay: leafbits_kernel reads the inverted leaves as expanded bitmaps)
-      bool rk = !no_rkey && !pk.invx.empty() && pk.leaf_words == 0;
-      int maxbits = 0, units = 0;
-      for (DevSeg& ds : pk.segs) {
-        ds.unit_begin = units;
-        units += (ds.ntiles + 31) / 32;
-        maxbits = std::max(maxbits, (int)ds.nbits);
-        int pairs = 0;
-        for (int k = 0; k < ds.nbits && rk; ++k) {
-          int found = -1;
-          for (size_t i = 0; i < pk.invx.size() && found < 0; ++i)
-            if (pk.invx[i].out == ds.bits_w[k]) found = (int)i;  // (word offsets until launch)
-          rk = found >= 0;
-          ds.inv_leaf[k] = found;
-          if (found >= 0) pairs += pk.invx[found].nids;
-        }
-        rk = rk && pairs <= PGPU_RKEY_PAIRS;
-      }
-      // the container table (every leaf's (id, key) records) and the unit's records and leaf images in LDS
-      int64_t ctab = 0;
-      for (InvLeafX& x : pk.invx) {
-        x.ctab_off = (int32_t)ctab;
-        ctab += (int64_t)x.nids * x.nkeys;
-      }
-      rk = rk && ctab <= INT32_MAX;
-      pk.rk_ctab_records = rk ? ctab : 0;
-      const size_t kdyn = rdyn + 16 * PGPU_RKEY_PAIRS + (size_t)std::max(1, maxbits) * 8192;
-      if (rk && kdyn <= PGPU_LDS_LIMIT) {
-        p.direct = 5;
-        p.total_units = units;
-        p.rk_leaves = std::max(1, maxbits);
-        // the aggregated columns' packed 16-bit ids instead of their value planes, values gathered per matched doc
-        // (PGPU_RKEY_IDS, read per plan): every value column a 16-bit dictionary column, <= 2
-        // non-COUNT aggregations (one queue half each)
-        int nq = 0;
-        for (int a = 0; a < p.nagg; ++a) nq += p.aggs[a].fn != PGPU_AGG_COUNT;
-        bool ids = nq >= 1 && nq <= 2;
-        for (const DevSeg& ds : pk.segs)
-          for (int c = 0; c < nv && ids && ds.ntiles; ++c) {
-            const DevColumn& vc = pk.cols[ds.col_begin + vcols[c]];
-            ids = vc.kind == PGPU_COL_FIXED_BIT && vc.bits == 16 && vc.dict != nullptr && vc.fwd != nullptr;
-          }
-        const char* ev = getenv("PGPU_RKEY_IDS");
-        p.rk_ids = ids && ev && atoi(ev) != 0 ? 1 : 0;
-        const int per_cu = (int)std::min<size_t>(nv > 1 && vbmax > 20 ? 2 : 3, PGPU_LDS_LIMIT / kdyn);
-        int gk = std::min<int64_t>((int64_t)ctx->num_cus * per_cu, std::max(1, units / 2));
-        if (gk >= 8) gk &= ~7;
-        grid = std::max(1, gk);
-        dyn = kdyn;
-      }
-    }
-  }
-  // candidate iteration from a sparse leading index leaf (query_kernel_cand; AndDocIdSet.java:87-140): every
-  // segment's dense program is one inclusive inverted leaf (a BITS leaf over its expansion) or sorted leaf holding at
-  // most kCandDensity of the segment's docs; the units are the inverted leaf's containers or the sorted ranges split
-  // at 65,536-doc keys, so the tiles without a doc of the leaf are never visited and the leaf is not expanded.  PGPU_NO_CAND=1 / PGPU_CAND_DENSITY (read per plan: tests).
-  pk.cand.clear();
-  if (p.direct == 1) {
-    const bool no_cand = getenv("PGPU_NO_CAND") && atoi(getenv("PGPU_NO_CAND")) != 0;
-    const double cand_max = getenv("PGPU_CAND_DENSITY") ? atof(getenv("PGPU_CAND_DENSITY")) : kCandDensity;
-    bool ok = !no_cand;
-    std::vector<uint32_t> units;  // {segment, container index (~0u: a sorted doc range), first doc, last doc}
-    std::vector<int> leaves;
-    for (int s = 0; s < (int)pk.segs.size() && ok; ++s) {
-      DevSeg& ds = pk.segs[s];
-      ds.unit_begin = (int32_t)(units.size() / 4);
-      ds.cand_leaf = -1;
-      if (ds.ntiles == 0) continue;
-      ok = ds.prog_len == 1 && ds.nstage == 0 && ds.fast == 0 && ds.nvstage == 0 && ds.single_bits == 0 &&
-           (ds.agg_mode == PGPU_AM_COUNT || ds.agg_mode == PGPU_AM_SPARSE);
-      if (!ok) break;
-      const DevInstr& in = pk.instrs[ds.prog_begin];
-      const pgpu_segment* sgm = q->segments[s].segment;
-      if (in.op == PGPU_I_SORTED) {  // SortedIndexBasedFilterOperator: doc ranges, split at container keys
-        ok = !in.negate;
-        int64_t docs = 0;
-        for (int k = 0; k < in.n && ok; ++k) docs += (int64_t)pk.pool[in.pool_off + 2 * k + 1] - pk.pool[in.pool_off + 2 * k] + 1;
-        ok = ok && (double)docs <= cand_max * (double)sgm->num_docs;
-        for (int k = 0; k < in.n && ok; ++k) {
-          for (int64_t lo = pk.pool[in.pool_off + 2 * k], hi = pk.pool[in.pool_off + 2 * k + 1]; lo <= hi;) {
-            const int64_t end = std::min<int64_t>(hi, (lo | 0xFFFF));
-            units.insert(units.end(), {(uint32_t)s, ~0u, (uint32_t)lo, (uint32_t)end});
-            lo = end + 1;
-          }
-        }
-        ok = ok && units.size() / 4 <= kCandMaxUnits;
+  int D = (int)std::max<int64_t>(2, std::min<int64_t>(8, 1 + (12 * 1024 + pk.tile_bytes - 1) / std::max<int64_t>(1, pk.tile_bytes)));
+  D = std::min(D, 1 + 63 / max_instrs);
+  static const int env_slots = env_int("PGPU_DIRECT_SLOTS");
+  if (env_slots >= 2) D = std::min(env_slots, 1 + 63 / max_instrs);
+  // as many 4-wave workgroups as LDS and VGPRs allow: 5 (20 waves) where the kernel fits 96 VGPRs
+  // (PGPU_DIRECT_MIN_WAVES), else 4 -- a fifth workgroup that cannot be resident only adds a tail
+  const int wgs = env_direct_wgs() >= 1 ? env_direct_wgs()
+                                        : ((p.mode == PGPU_MODE_GLOBAL || p.mode == PGPU_MODE_HASH) ? 5 : 4);
+  auto ddyn_of = [&](int d) { return (size_t)4 * p.cons_bytes + align16(p.ltab_bytes) + (size_t)4 * d * p.slot_bytes; };
+  while (D > 2 && wgs * ddyn_of(D) > PGPU_LDS_LIMIT) --D;
+  const size_t ddyn = ddyn_of(D);
+  if (D < 2 || ddyn > PGPU_LDS_LIMIT) return;
+  p.direct = PGPU_KV_DIRECT;
+  p.dslots = D;
+  p.min_instrs = std::max(1, min_instrs);
+  pl.grid = stream_grid(num_cus, (int)std::min<size_t>(wgs, PGPU_LDS_LIMIT / ddyn), p.total_tiles, 16);
+  pl.dyn = ddyn;
+}
+
+// register-direct (query_kernel_rdirect): one bit-sliced fast leaf of <= 16 bits per segment is the only staged
+// column -- its planes stream into VGPRs, no LDS slots (tools/stream_bench.hip: 5.6-6.0 TB/s)
+void try_rdirect(int num_cus, const Packer& pk, DevParams& p, LaunchPlan& pl) {
+  static const bool no_rdirect = env_flag("PGPU_NO_RDIRECT");
+  bool rd = !no_rdirect;
+  int rd_bits = 1;
+  for (const DevSeg& ds : pk.segs)
+    if (ds.ntiles) {
+      if (!(ds.nstage == 1 && ds.fast == 1 && ds.stage_sliced == 1) || ds.agg_mode == PGPU_AM_SLICED) {
+        rd = false;
         continue;
       }
-      ok = in.op == PGPU_I_BITS;
-      if (!ok) break;
-      int leaf = -1;
-      for (size_t i = 0; i < pk.invx.size() && leaf < 0; ++i)
-        if (pk.invx[i].out == in.fwd) leaf = (int)i;  // (word offsets until launch)
-      ok = leaf >= 0 && !pk.invx[leaf].negate && in.col >= 0 && in.col < q->num_columns;
-      if (!ok) break;
-      const InvLeafX& x = pk.invx[leaf];
-      const HostColumn& h = sgm->cols[q->segments[s].column_map[in.col]];
-      const DevColumn& dc = pk.cols[ds.col_begin + in.col];
-      ok = (x.nids == 1 || dc.kind == PGPU_COL_FIXED_BIT || dc.kind == PGPU_COL_RAW) &&
-           h.inv_hdir.size() == (size_t)h.inv_card + 1 && h.inv_cards.size() == (size_t)h.inv_card;
-      const int32_t* ids = pk.invids.data() + (intptr_t)x.ids;
-      double docs = 0;
-      for (int k = 0; k < x.nids && ok; ++k) {
-        ok = ids[k] >= 0 && ids[k] < h.inv_card;
-        if (ok) docs += h.inv_cards[ids[k]];
+      const DevColumn& c = pk.cols[ds.col_begin + ds.stage_col[0]];
+      rd &= c.bits >= 1 && c.bits <= 16;
+      rd_bits = std::max(rd_bits, (int)c.bits);
+    }
+  const size_t rdyn = reg_kernel_lds(p);
+  if (!rd || rdyn > PGPU_LDS_LIMIT) return;
+  // 104-126 VGPRs (4 waves per SIMD) except the aggregation-only mode (136-152: 3)
+  const int per_cu = (int)std::min<size_t>(env_direct_wgs() >= 1 ? env_direct_wgs() : (p.mode == PGPU_MODE_AGG ? 3 : 4),
+                                           PGPU_LDS_LIMIT / rdyn);
+  p.direct = PGPU_KV_RDIRECT;
+  p.rd_planes = rd_bits <= 8 ? 8 : rd_bits <= 10 ? 10 : rd_bits <= 12 ? 12 : 16;
+  // prefix pre-filter when every segment's residual leaf has one (plan_prefix)
+  bool pfx = true;
+  for (const DevSeg& ds : pk.segs) pfx &= ds.ntiles == 0 || ds.pfx_col >= 0;
+  p.rd_pfx = pfx && p.rd_planes <= 12 ? PGPU_PFX_PLANES : 0;  // (no 16 + 3-plane variant: > 128 VGPRs)
+  p.dslots = 0;
+  pl.grid = stream_grid(num_cus, per_cu, p.total_tiles, 16);
+  pl.dyn = rdyn;
+}
+
+// register streaming (query_kernel_rstream): aggregation-only, every segment an AND of two bit-sliced fast
+// leaves (<= 16 and <= 8 bits) with its aggregations all answered from one column's value planes (<= 24)
+void try_rstream(int num_cus, const Packer& pk, DevParams& p, LaunchPlan& pl) {
+  const size_t rdyn = reg_kernel_lds(p);
+  bool rs = !env_flag("PGPU_NO_RSTREAM") && p.mode == PGPU_MODE_AGG && rdyn <= PGPU_LDS_LIMIT;  // per plan (tests)
+  int vcol = -1, rs_narrow = 1, rs_vb = 1;
+  for (int a = 0; a < p.nagg && rs; ++a) {
+    const DevAgg& ag = p.aggs[a];
+    if (ag.fn == PGPU_AGG_COUNT) continue;
+    rs = (vcol < 0 || vcol == ag.col) && value_plane_agg(ag);
+    vcol = ag.col;
+  }
+  rs = rs && vcol >= 0;
+  for (const DevSeg& ds : pk.segs) {
+    if (!rs || !ds.ntiles) continue;
+    rs = ds.nstage == 2 && ds.fast == 2 && ds.stage_sliced == 3 && ds.agg_mode == PGPU_AM_SLICED &&
+         ds.rprog_len == 0 && ds.f_nr[0] > 0 && ds.f_nr[1] > 0;
+    if (!rs) break;
+    const DevColumn& vc = pk.cols[ds.col_begin + vcol];
+    int b[2];
+    for (int j = 0; j < 2; ++j) b[j] = pk.cols[ds.col_begin + pk.instrs[ds.prog_begin + ds.fast_ins[j]].col].bits;
+    rs = vc.vsliced && vc.vbits >= 1 && vc.vbits <= 24 && std::max(b[0], b[1]) <= 16 && std::min(b[0], b[1]) >= 1 &&
+         std::min(b[0], b[1]) <= 8;
+    rs_narrow = std::max(rs_narrow, std::min(b[0], b[1]));
+    rs_vb = std::max(rs_vb, (int)vc.vbits);
+  }
+  if (!rs) return;
+  const int per_cu = (int)std::min<size_t>(env_direct_wgs() >= 1 ? env_direct_wgs() : 3, PGPU_LDS_LIMIT / rdyn);
+  p.direct = PGPU_KV_RSTREAM;
+  p.rd_planes = rs_narrow <= 4 ? 4 : 8;
+  p.rs_vplanes = rs_vb <= 16 ? 16 : 24;
+  p.rd_pfx = 0;
+  p.dslots = 0;
+  pl.grid = stream_grid(num_cus, per_cu, p.total_tiles, 16);
+  pl.dyn = rdyn;
+}
+
+// rkey (query_kernel_rkey), from rprog only: every BITS leaf an inverted one -- read the containers per (segment,
+// container key) unit into LDS instead of expanding them into HBM bitmaps first.  The unit numbering, the leaves'
+// indices and the container-table offsets are written into the segments and leaves whether or not it is taken.
+void try_rkey(int num_cus, Packer& pk, DevParams& p, LaunchPlan& pl, const int* vcols, int nv, int vbmax) {
+  // (not under the exact-statistics replay: leafbits_kernel reads the inverted leaves as expanded bitmaps)
+  bool rk = !env_flag("PGPU_NO_RKEY") && !pk.invx.empty() && pk.leaf_words == 0;  // per plan (tests)
+  int maxbits = 0, units = 0;
+  for (DevSeg& ds : pk.segs) {
+    ds.unit_begin = units;
+    units += (ds.ntiles + 31) / 32;
+    maxbits = std::max(maxbits, (int)ds.nbits);
+    int pairs = 0;
+    for (int k = 0; k < ds.nbits && rk; ++k) {
+      int found = -1;
+      for (size_t i = 0; i < pk.invx.size() && found < 0; ++i)
+        if (pk.invx[i].out == ds.bits_w[k]) found = (int)i;  // (word offsets until launch)
+      rk = found >= 0;
+      ds.inv_leaf[k] = found;
+      if (found >= 0) pairs += pk.invx[found].nids;
+    }
+    rk = rk && pairs <= PGPU_RKEY_PAIRS;
+  }
+  // the container table (every leaf's (id, key) records) and the unit's records and leaf images in LDS
+  int64_t ctab = 0;
+  for (InvLeafX& x : pk.invx) {
+    x.ctab_off = (int32_t)ctab;
+    ctab += (int64_t)x.nids * x.nkeys;
+  }
+  rk = rk && ctab <= INT32_MAX;
+  pk.rk_ctab_records = rk ? ctab : 0;
+  const size_t kdyn = reg_kernel_lds(p) + 16 * PGPU_RKEY_PAIRS + (size_t)std::max(1, maxbits) * 8192;
+  if (!rk || kdyn > PGPU_LDS_LIMIT) return;
+  p.direct = PGPU_KV_RKEY;
+  p.total_units = units;
+  p.rk_leaves = std::max(1, maxbits);
+  // the aggregated columns' packed 16-bit ids instead of their value planes, values gathered per matched doc
+  // (PGPU_RKEY_IDS, read per plan): every value column a 16-bit dictionary column, <= 2
+  // non-COUNT aggregations (one queue half each)
+  int nq = 0;
+  for (int a = 0; a < p.nagg; ++a) nq += p.aggs[a].fn != PGPU_AGG_COUNT;
+  bool ids = nq >= 1 && nq <= 2;
+  for (const DevSeg& ds : pk.segs)
+    for (int c = 0; c < nv && ids && ds.ntiles; ++c) {
+      const DevColumn& vc = pk.cols[ds.col_begin + vcols[c]];
+      ids = vc.kind == PGPU_COL_FIXED_BIT && vc.bits == 16 && vc.dict != nullptr && vc.fwd != nullptr;
+    }
+  p.rk_ids = ids && env_flag("PGPU_RKEY_IDS") ? 1 : 0;
+  const int per_cu = (int)std::min<size_t>(nv > 1 && vbmax > 20 ? 2 : 3, PGPU_LDS_LIMIT / kdyn);
+  pl.grid = stream_grid(num_cus, per_cu, units, 2);
+  pl.dyn = kdyn;
+}
+
+// register streaming of index-only programs (query_kernel_rprog), from direct only: aggregation-only, every
+// segment's dense program a truth table over <= 5 bitmap / sorted leaves, its aggregations from <= 2 columns'
+// value planes (<= 24).  When taken, rkey is tried on top of it.
+void try_rprog(int num_cus, Packer& pk, DevParams& p, LaunchPlan& pl) {
+  if (p.direct != PGPU_KV_DIRECT || p.mode != PGPU_MODE_AGG) return;
+  bool rp = !env_flag("PGPU_NO_RPROG");  // per plan (tests)
+  int vcols[2] = {-1, -1}, nv = 0, vbmax = 1;
+  for (int a = 0; a < p.nagg && rp; ++a) {
+    const DevAgg& ag = p.aggs[a];
+    if (ag.fn == PGPU_AGG_COUNT || ag.col == vcols[0] || ag.col == vcols[1]) continue;
+    rp = nv < 2 && value_plane_agg(ag);
+    if (rp) vcols[nv++] = ag.col;
+  }
+  for (int a = 0; a < p.nagg && rp; ++a)  // (every aggregation over a value column must be a value-plane one)
+    if (p.aggs[a].fn != PGPU_AGG_COUNT) rp = value_plane_agg(p.aggs[a]);
+  rp = rp && nv >= 1;
+  for (DevSeg& ds : pk.segs) {
+    if (!rp || !ds.ntiles) continue;
+    rp = ds.nstage == 0 && ds.fast == 0 && ds.agg_mode == PGPU_AM_SLICED && ds.rprog_len == 0 && ds.nvstage == 0 &&
+         program_truth_table(pk, ds);
+    for (int c = 0; c < nv && rp; ++c) {
+      const DevColumn& vc = pk.cols[ds.col_begin + vcols[c]];
+      rp = vc.vsliced && vc.vbits >= 1 && vc.vbits <= 24;
+      vbmax = std::max(vbmax, (int)vc.vbits);
+    }
+  }
+  const size_t rdyn = reg_kernel_lds(p);
+  if (!rp || rdyn > PGPU_LDS_LIMIT) return;
+  const int per_cu = (int)std::min<size_t>(env_direct_wgs() >= 1 ? env_direct_wgs() : (nv > 1 && vbmax > 20 ? 2 : 3),
+                                           PGPU_LDS_LIMIT / rdyn);
+  p.direct = PGPU_KV_RPROG;
+  p.rd_planes = nv;
+  p.rs_vplanes = vbmax <= 16 ? 16 : (vbmax <= 20 && nv > 1) ? 20 : 24;
+  p.rd_pfx = 0;
+  p.dslots = 0;
+  pl.grid = stream_grid(num_cus, per_cu, p.total_tiles, 16);
+  pl.dyn = rdyn;
+  try_rkey(num_cus, pk, p, pl, vcols, nv, vbmax);
+}
+
+// candidate iteration from a sparse leading index leaf (query_kernel_cand; AndDocIdSet.java:87-140), from direct
+// only: every segment's dense program is one inclusive inverted leaf (a BITS leaf over its expansion) or sorted
+// leaf holding at most kCandDensity of the segment's docs; the units are the inverted leaf's containers or the
+// sorted ranges split at 65,536-doc keys, so the tiles without a doc of the leaf are never visited and the leaf is
+// not expanded.  PGPU_NO_CAND=1 / PGPU_CAND_DENSITY (read per plan: tests).  The attempt numbers the segments'
+// units and names their leaves as it goes; a failed one resets the leaves.
+void try_cand(int num_cus, const pgpu_query_desc* q, Packer& pk, DevParams& p, LaunchPlan& pl) {
+  pk.cand.clear();
+  if (p.direct != PGPU_KV_DIRECT) return;
+  const double cand_max = getenv("PGPU_CAND_DENSITY") ? atof(getenv("PGPU_CAND_DENSITY")) : kCandDensity;
+  bool ok = !env_flag("PGPU_NO_CAND");
+  std::vector<uint32_t> units;  // {segment, container index (~0u: a sorted doc range), first doc, last doc}
+  std::vector<int> leaves;
+  for (int s = 0; s < (int)pk.segs.size() && ok; ++s) {
+    DevSeg& ds = pk.segs[s];
+    ds.unit_begin = (int32_t)(units.size() / 4);
+    ds.cand_leaf = -1;
+    if (ds.ntiles == 0) continue;
+    ok = ds.prog_len == 1 && ds.nstage == 0 && ds.fast == 0 && ds.nvstage == 0 && ds.single_bits == 0 &&
+         (ds.agg_mode == PGPU_AM_COUNT || ds.agg_mode == PGPU_AM_SPARSE);
+    if (!ok) break;
+    const DevInstr& in = pk.instrs[ds.prog_begin];
+    const pgpu_segment* sgm = q->segments[s].segment;
+    if (in.op == PGPU_I_SORTED) {  // SortedIndexBasedFilterOperator: doc ranges, split at container keys
+      ok = !in.negate;
+      int64_t docs = 0;
+      for (int k = 0; k < in.n && ok; ++k) docs += (int64_t)pk.pool[in.pool_off + 2 * k + 1] - pk.pool[in.pool_off + 2 * k] + 1;
+      ok = ok && (double)docs <= cand_max * (double)sgm->num_docs;
+      for (int k = 0; k < in.n && ok; ++k) {
+        for (int64_t lo = pk.pool[in.pool_off + 2 * k], hi = pk.pool[in.pool_off + 2 * k + 1]; lo <= hi;) {
+          const int64_t end = std::min<int64_t>(hi, (lo | 0xFFFF));
+          units.insert(units.end(), {(uint32_t)s, ~0u, (uint32_t)lo, (uint32_t)end});
+          lo = end + 1;
+        }
       }
-      ok = ok && docs <= cand_max * (double)sgm->num_docs;
-      // at most one container per tile of the segment: past that the tile sweep is as cheap, and a long IN list's
-      // containers would cost the host more to list than the sweep costs the GPU
-      uint64_t nct = 0;
-      for (int k = 0; k < x.nids && ok; ++k) nct += h.inv_hdir[ids[k] + 1] - h.inv_hdir[ids[k]];
-      ok = ok && nct <= (uint64_t)ds.ntiles;
-      for (int k = 0; k < x.nids && ok; ++k)
-        for (uint32_t c = h.inv_hdir[ids[k]]; c < h.inv_hdir[ids[k] + 1]; ++c) units.insert(units.end(), {(uint32_t)s, c, 0u, 0u});
       ok = ok && units.size() / 4 <= kCandMaxUnits;
-      ds.cand_leaf = leaf;
-      leaves.push_back(leaf);
+      continue;
     }
-    // a wave's consumer area and 8 KiB container image; four waves per workgroup
-    const size_t cdyn = (size_t)4 * p.cons_bytes + align16(p.ltab_bytes) + (size_t)4 * 8192;
-    if (ok && cdyn <= PGPU_LDS_LIMIT) {
-      const int nu = (int)(units.size() / 4);
-      const int per_cu = (int)std::min<size_t>(4, PGPU_LDS_LIMIT / cdyn);
-      const int g = (int)std::min<int64_t>((int64_t)ctx->num_cus * per_cu, std::max(1, (nu + 3) / 4));
-      p.direct = 6;
-      p.total_units = nu;
-      grid = std::max(1, g);
-      dyn = cdyn;
-      pk.cand.swap(units);
-      // the iterated leaves need no doc bitmap unless the exact-statistics replay or a residual program reads it
-      std::vector<const uint32_t*> read;
-      for (const DevSeg& ds : pk.segs)
-        for (int i = ds.rprog_begin; i < ds.rprog_begin + ds.rprog_len; ++i)
-          if (pk.instrs[i].op == PGPU_I_BITS) read.push_back(pk.instrs[i].fwd);
-      if (pk.leaf_words == 0)
-        for (int lf : leaves)
-          if (std::find(read.begin(), read.end(), pk.invx[lf].out) == read.end()) pk.invx[lf].skip = 1;
-    } else {
-      for (DevSeg& ds : pk.segs) ds.cand_leaf = -1;
+    ok = in.op == PGPU_I_BITS;
+    if (!ok) break;
+    int leaf = -1;
+    for (size_t i = 0; i < pk.invx.size() && leaf < 0; ++i)
+      if (pk.invx[i].out == in.fwd) leaf = (int)i;  // (word offsets until launch)
+    ok = leaf >= 0 && !pk.invx[leaf].negate && in.col >= 0 && in.col < q->num_columns;
+    if (!ok) break;
+    const InvLeafX& x = pk.invx[leaf];
+    const HostColumn& h = sgm->cols[q->segments[s].column_map[in.col]];
+    const DevColumn& dc = pk.cols[ds.col_begin + in.col];
+    ok = (x.nids == 1 || dc.kind == PGPU_COL_FIXED_BIT || dc.kind == PGPU_COL_RAW) &&
+         h.inv_hdir.size() == (size_t)h.inv_card + 1 && h.inv_cards.size() == (size_t)h.inv_card;
+    const int32_t* ids = pk.invids.data() + (intptr_t)x.ids;
+    double docs = 0;
+    for (int k = 0; k < x.nids && ok; ++k) {
+      ok = ids[k] >= 0 && ids[k] < h.inv_card;
+      if (ok) docs += h.inv_cards[ids[k]];
     }
+    ok = ok && docs <= cand_max * (double)sgm->num_docs;
+    // at most one container per tile of the segment: past that the tile sweep is as cheap, and a long IN list's
+    // containers would cost the host more to list than the sweep costs the GPU
+    uint64_t nct = 0;
+    for (int k = 0; k < x.nids && ok; ++k) nct += h.inv_hdir[ids[k] + 1] - h.inv_hdir[ids[k]];
+    ok = ok && nct <= (uint64_t)ds.ntiles;
+    for (int k = 0; k < x.nids && ok; ++k)
+      for (uint32_t c = h.inv_hdir[ids[k]]; c < h.inv_hdir[ids[k] + 1]; ++c) units.insert(units.end(), {(uint32_t)s, c, 0u, 0u});
+    ok = ok && units.size() / 4 <= kCandMaxUnits;
+    ds.cand_leaf = leaf;
+    leaves.push_back(leaf);
   }
-  // the reference's numEntriesScannedInFilter fused into the register stream (query_kernel_rfsm): on the
-  // register-direct path with every segment an AND of two bit-sliced leaves (andfsm's two-leaf build), both leaves'
-  // planes are streamed once for the query and the tile maps together (PGPU_NO_RFSM=1, read per plan: tests)
-  if (p.direct == 2 && pk.fsm && pk.fsm_s2 && p.mode != PGPU_MODE_PART &&
-      !(getenv("PGPU_NO_RFSM") && atoi(getenv("PGPU_NO_RFSM")) != 0)) {
-    int b0 = 1, b1 = 1;
-    for (const DevSeg& ds : pk.segs)
-      if (ds.ntiles && ds.leaf_len == 2) {
-        b0 = std::max(b0, (int)pk.instrs[pk.pool[ds.leaf_begin]].bits);
-        b1 = std::max(b1, (int)pk.instrs[pk.pool[ds.leaf_begin + 1]].bits);
-      }
-    const size_t rdyn = (size_t)4 * p.cons_bytes + align16(p.ltab_bytes) + 16;
-    if (b0 <= 16 && b1 <= 24 && rdyn <= PGPU_LDS_LIMIT) {
-      const bool small = b0 <= 12 && b1 <= 20;
-      // 142-167 VGPRs: three waves per SIMD; the aggregation-only mode's 183-199: two
-      const int per_cu = (int)std::min<size_t>(p.mode == PGPU_MODE_AGG ? 2 : 3, PGPU_LDS_LIMIT / rdyn);
-      int g = std::min<int64_t>((int64_t)ctx->num_cus * per_cu, std::max(1, p.total_tiles / 16));
-      if (g >= 8) g &= ~7;
-      p.direct = 8;
-      p.rd_planes = small ? (b0 <= 10 ? 10 : 12) : 16;
-      p.rs_vplanes = small ? 20 : 24;
-      p.rd_pfx = 0;
-      p.dslots = 0;
-      grid = std::max(1, g);
-      dyn = rdyn;
-    }
+  // a wave's consumer area and 8 KiB container image; four waves per workgroup
+  const size_t cdyn = (size_t)4 * p.cons_bytes + align16(p.ltab_bytes) + (size_t)4 * 8192;
+  if (!ok || cdyn > PGPU_LDS_LIMIT) {
+    for (DevSeg& ds : pk.segs) ds.cand_leaf = -1;
+    return;
   }
-  // sliced aggregation runs in the self-loading kernels only (query_kernel_direct, and query_kernel_rstream with the
-  // value planes in VGPRs): elsewhere its segments gather per candidate (their staged aggregation planes are then
-  // only extra DMA, never read)
-  if (p.direct != 1)
-    for (DevSeg& ds : pk.segs) {
-      if (ds.agg_mode == PGPU_AM_SLICED && p.direct != 3 && p.direct != 4) ds.agg_mode = PGPU_AM_SPARSE;
-      for (int j = 0; j < ds.nvstage; ++j)  // (the ring loaders stage filter columns only)
-        ds.stage_instrs -= (pk.cols[ds.col_begin + ds.vstage_col[j]].vbits + 3) / 4;
-      ds.nvstage = 0;
+  const int nu = (int)(units.size() / 4);
+  const int per_cu = (int)std::min<size_t>(4, PGPU_LDS_LIMIT / cdyn);
+  p.direct = PGPU_KV_CAND;
+  p.total_units = nu;
+  pl.grid = std::max(1, (int)std::min<int64_t>((int64_t)num_cus * per_cu, std::max(1, (nu + 3) / 4)));
+  pl.dyn = cdyn;
+  pk.cand.swap(units);
+  // the iterated leaves need no doc bitmap unless the exact-statistics replay or a residual program reads it
+  std::vector<const uint32_t*> read;
+  for (const DevSeg& ds : pk.segs)
+    for (int i = ds.rprog_begin; i < ds.rprog_begin + ds.rprog_len; ++i)
+      if (pk.instrs[i].op == PGPU_I_BITS) read.push_back(pk.instrs[i].fwd);
+  if (pk.leaf_words == 0)
+    for (int lf : leaves)
+      if (std::find(read.begin(), read.end(), pk.invx[lf].out) == read.end()) pk.invx[lf].skip = 1;
+}
+
+// the reference's numEntriesScannedInFilter fused into the register stream (query_kernel_rfsm), from rdirect only:
+// with every segment an AND of two bit-sliced leaves (andfsm's two-leaf build), both leaves' planes are streamed
+// once for the query and the tile maps together (PGPU_NO_RFSM=1, read per plan: tests)
+void try_rfsm(int num_cus, const Packer& pk, DevParams& p, LaunchPlan& pl) {
+  if (p.direct != PGPU_KV_RDIRECT || !pk.fsm || !pk.fsm_s2 || p.mode == PGPU_MODE_PART || env_flag("PGPU_NO_RFSM"))
+    return;
+  int b0 = 1, b1 = 1;
+  for (const DevSeg& ds : pk.segs)
+    if (ds.ntiles && ds.leaf_len == 2) {
+      b0 = std::max(b0, (int)pk.instrs[pk.pool[ds.leaf_begin]].bits);
+      b1 = std::max(b1, (int)pk.instrs[pk.pool[ds.leaf_begin + 1]].bits);
     }
-  // one-word PART records (in-partition key, dict id) when every segment holds the same dictionary for the
-  // aggregated column (the common case of one table's segments sharing value sets): half the record traffic
-  int part_idbits = 0;
-  const void* part_pdict = nullptr;
-  if (p.mode == PGPU_MODE_PART && pcol >= 0) {
-    const HostColumn* h0 = &q->segments[0].segment->cols[q->segments[0].column_map[pcol]];
+  const size_t rdyn = reg_kernel_lds(p);
+  if (b0 > 16 || b1 > 24 || rdyn > PGPU_LDS_LIMIT) return;
+  const bool small = b0 <= 12 && b1 <= 20;
+  // 142-167 VGPRs: three waves per SIMD; the aggregation-only mode's 183-199: two
+  const int per_cu = (int)std::min<size_t>(p.mode == PGPU_MODE_AGG ? 2 : 3, PGPU_LDS_LIMIT / rdyn);
+  p.direct = PGPU_KV_RFSM;
+  p.rd_planes = small ? (b0 <= 10 ? 10 : 12) : 16;
+  p.rs_vplanes = small ? 20 : 24;
+  p.rd_pfx = 0;
+  p.dslots = 0;
+  pl.grid = stream_grid(num_cus, per_cu, p.total_tiles, 16);
+  pl.dyn = rdyn;
+}
+
+// sliced aggregation runs in the self-loading kernels only (query_kernel_direct, and query_kernel_rstream /
+// query_kernel_rprog with the value planes in VGPRs): elsewhere its segments gather per candidate (their staged
+// aggregation planes are then only extra DMA, never read)
+void demote_sliced_agg(Packer& pk, const DevParams& p) {
+  if (p.direct == PGPU_KV_DIRECT) return;
+  for (DevSeg& ds : pk.segs) {
+    if (ds.agg_mode == PGPU_AM_SLICED && p.direct != PGPU_KV_RSTREAM && p.direct != PGPU_KV_RPROG)
+      ds.agg_mode = PGPU_AM_SPARSE;
+    for (int j = 0; j < ds.nvstage; ++j)  // (the ring loaders stage filter columns only)
+      ds.stage_instrs -= (pk.cols[ds.col_begin + ds.vstage_col[j]].vbits + 3) / 4;
+    ds.nvstage = 0;
+  }
+}
+
+const HostColumn& part_column(const pgpu_query_desc* q, int s, int pcol) {
+  return q->segments[s].segment->cols[q->segments[s].column_map[pcol]];
+}
+
+// PART phase 2 needs the carried column's values (a SUM section), not only its dictionary ids
+bool part_needs_values(const pgpu_table_layout& L) {
+  bool need_val = false;
+  for (int s = 1; s < L.num_sections; ++s)
+    need_val |= L.section_op[s] == PGPU_RED_SUM_I64 || L.section_op[s] == PGPU_RED_SUM_F64;
+  return need_val;
+}
+
+// PART record geometry.  One-word records (in-partition key, dict id) when every segment holds the same dictionary
+// for the aggregated column (the common case of one table's segments sharing value sets): half the record traffic.
+// Phase 2 then reads SUM values from an LDS copy of that dictionary when it fits beside the partition's table,
+// instead of gathering them from L2 (one 128-B line per 4-B lookup).
+void plan_part_records(const pgpu_query_desc* q, const pgpu_table_layout& L, const DevParams& p, LaunchPlan& pl) {
+  if (p.mode == PGPU_MODE_PART && pl.pcol >= 0) {
+    const HostColumn* h0 = &part_column(q, 0, pl.pcol);
     bool shared = h0->dict_card > 0 && !h0->hdict.empty();
     for (int s = 1; s < q->num_segments && shared; ++s) {
-      const HostColumn* h = &q->segments[s].segment->cols[q->segments[s].column_map[pcol]];
+      const HostColumn* h = &part_column(q, s, pl.pcol);
       shared = h->dict_card == h0->dict_card && h->dict_type == h0->dict_type && h->dict_hash[0] == h0->dict_hash[0] &&
                h->dict_hash[1] == h0->dict_hash[1];
     }
     int idbits = 1;
     while (idbits < 31 && (1ll << idbits) < h0->dict_card) ++idbits;
-    if (shared && pshift + idbits <= 32 && !(q->flags & PGPU_Q_PART_SPILL)) {
-      part_idbits = idbits;
-      part_pdict = h0->dict.p;
+    if (shared && pl.pshift + idbits <= 32 && !(q->flags & PGPU_Q_PART_SPILL)) {
+      pl.part_idbits = idbits;
+      pl.part_pdict = h0->dict.p;
     }
   }
-  const int part_rw = pcol >= 0 && !part_idbits ? 2 : 1;
-  // phase 2 reads SUM values from an LDS copy of the shared dictionary when it fits beside the partition's table,
-  // instead of gathering them from L2 (one 128-B line per 4-B lookup)
-  int slice_shift = 0, ldict = 0;
-  uint32_t pdict_n = 0;
-  int for_old_pshift = -1;
-  uint64_t for_old_nparts = 0;
-  const HostColumn* for_h = nullptr;
-  if (part_idbits) {
-    const HostColumn* h0 = &q->segments[0].segment->cols[q->segments[0].column_map[pcol]];
-    pdict_n = (uint32_t)h0->dict_card;
-    bool need_val = false;
-    for (int s = 1; s < L.num_sections; ++s)
-      need_val |= L.section_op[s] == PGPU_RED_SUM_I64 || L.section_op[s] == PGPU_RED_SUM_F64;
-    while ((1ull << slice_shift) < pdict_n) ++slice_shift;
-    static const bool no_ldict = getenv("PGPU_NO_LDICT") && atoi(getenv("PGPU_NO_LDICT")) != 0;
-    ldict = need_val && !no_ldict && (8ull * L.num_sections << pshift) + (4ull << slice_shift) <= PGPU_LDS_LIMIT;
-    // too large to copy whole: its frame-of-reference image, beside a table of fewer keys per partition
-    static const bool no_for = getenv("PGPU_NO_FOR") && atoi(getenv("PGPU_NO_FOR")) != 0;
-    if (need_val && !ldict && !no_for && h0->for_bits > 0 && h0->dict_type == PGPU_INT) {
-      const uint64_t fb = 4ull * ((uint64_t)h0->for_nblk * (1 + h0->for_bits) + 1);
-      // fewer keys per partition means more phase-1 partitions and shallower LDS rings per partition, which
-      // skewed keys pay for (config 4 Zipf(1.1): 24 -> 39 ms at 2048 keys); only the unchanged geometry is used
-      // unless PGPU_FOR_SHRINK=1
-      // the compact phase-2 table: count and MIN / MAX ids in 4 B, SUM sections in 8 B per key
-      uint64_t per_key = 4;
-      for (int s = 1; s < L.num_sections; ++s)
-        per_key += L.section_op[s] == PGPU_RED_SUM_I64 || L.section_op[s] == PGPU_RED_SUM_F64 ? 8 : 4;
-      static const bool shrink = getenv("PGPU_FOR_SHRINK") && atoi(getenv("PGPU_FOR_SHRINK")) != 0;
-      int ps = pshift;
-      while (shrink && ps > 9 && (per_key << ps) + fb > PGPU_LDS_LIMIT) --ps;
-      const uint64_t np2 = (L.num_keys + (1ull << ps) - 1) >> ps;
-      if ((per_key << ps) + fb <= PGPU_LDS_LIMIT && np2 <= PGPU_PSCAN_MAX_PARTS &&
-          np2 <= PGPU_PART_MAX_PARTS && ps + part_idbits <= 32) {
-        for_old_pshift = pshift;
-        for_old_nparts = nparts;
-        pshift = ps;
-        nparts = np2;
-        ldict = 2;
-        for_h = h0;
-      }
-    }
+  pl.part_rw = pl.pcol >= 0 && !pl.part_idbits ? 2 : 1;
+  if (!pl.part_idbits) return;
+  pl.pdict_n = (uint32_t)part_column(q, 0, pl.pcol).dict_card;
+  while ((1ull << pl.slice_shift) < pl.pdict_n) ++pl.slice_shift;
+  static const bool no_ldict = env_flag("PGPU_NO_LDICT");
+  pl.ldict = part_needs_values(L) && !no_ldict &&
+             (8ull * L.num_sections << pl.pshift) + (4ull << pl.slice_shift) <= PGPU_LDS_LIMIT;
+}
+
+// A dictionary too large to copy whole into LDS: its frame-of-reference image, beside a table of fewer keys per
+// partition.  True (with the geometry in *ps / *np) when phase 2 could run that way.
+bool for_image_fits(const pgpu_query_desc* q, const pgpu_table_layout& L, const LaunchPlan& pl, int* ps,
+                    uint64_t* np) {
+  static const bool no_for = env_flag("PGPU_NO_FOR");
+  if (!pl.part_idbits || !part_needs_values(L) || pl.ldict || no_for) return false;
+  const HostColumn& h0 = part_column(q, 0, pl.pcol);
+  if (!(h0.for_bits > 0 && h0.dict_type == PGPU_INT)) return false;
+  const uint64_t fb = 4ull * ((uint64_t)h0.for_nblk * (1 + h0.for_bits) + 1);
+  // fewer keys per partition means more phase-1 partitions and shallower LDS rings per partition, which
+  // skewed keys pay for (config 4 Zipf(1.1): 24 -> 39 ms at 2048 keys); only the unchanged geometry is used
+  // unless PGPU_FOR_SHRINK=1
+  // the compact phase-2 table: count and MIN / MAX ids in 4 B, SUM sections in 8 B per key
+  uint64_t per_key = 4;
+  for (int s = 1; s < L.num_sections; ++s)
+    per_key += L.section_op[s] == PGPU_RED_SUM_I64 || L.section_op[s] == PGPU_RED_SUM_F64 ? 8 : 4;
+  static const bool shrink = env_flag("PGPU_FOR_SHRINK");
+  *ps = pl.pshift;
+  while (shrink && *ps > 9 && (per_key << *ps) + fb > PGPU_LDS_LIMIT) --*ps;
+  *np = (L.num_keys + (1ull << *ps) - 1) >> *ps;
+  return (per_key << *ps) + fb <= PGPU_LDS_LIMIT && *np <= PGPU_PSCAN_MAX_PARTS && *np <= PGPU_PART_MAX_PARTS &&
+         *ps + pl.part_idbits <= 32;
+}
+
+// pscan (part_scan_kernel): a partitioned group-by whose segments need no candidate queue runs phase 1 on
+// self-loading waves, records written through per-partition LDS rings of >= two 128-B lines; two workgroups per CU
+// when the rings fit, else one.  Replaces whatever variant was chosen (DevParams::direct back to PGPU_KV_RING).
+// Only this phase 1 can feed a phase 2 that reads the frame-of-reference image, so that geometry is tried here and
+// rolled back when pscan is not taken: the ring's partition counters were sized for the original geometry.
+void try_pscan(int num_cus, const pgpu_query_desc* q, const pgpu_table_layout& L, const Packer& pk, DevParams& p,
+               LaunchPlan& pl) {
+  const int old_pshift = pl.pshift;
+  const uint64_t old_nparts = pl.nparts;
+  int for_ps = 0;
+  uint64_t for_np = 0;
+  if (for_image_fits(q, L, pl, &for_ps, &for_np)) {
+    pl.pshift = for_ps;
+    pl.nparts = for_np;
+    pl.ldict = 2;
+    pl.for_h = &part_column(q, 0, pl.pcol);
   }
-  // partitioned group-by whose segments need no candidate queue: phase 1 by part_scan_kernel (self-loading waves,
-  // records written through per-partition LDS rings of >= two 128-B lines); two workgroups per CU when the rings
-  // fit, else one
-  static const bool no_pscan = getenv("PGPU_NO_PSCAN") && atoi(getenv("PGPU_NO_PSCAN")) != 0;
+  static const bool no_pscan = env_flag("PGPU_NO_PSCAN");
   p.pscan = 0;
-  const uint64_t ptotal = nparts;
+  const uint64_t ptotal = pl.nparts;
   if (!no_pscan && p.mode == PGPU_MODE_PART && ptotal <= PGPU_PSCAN_MAX_PARTS) {
     bool ok = true;
     for (const DevSeg& ds : pk.segs) ok &= ds.rprog_len == 0;
     const size_t wave_bytes = 256 * (size_t)p.mask_rows;
-    const size_t fixed_b = 16 * ((ptotal + 66) & ~1ull) + 4 * 64 * part_rw + 4 * wave_bytes;  // + caps, dummies, cancel
-    const uint64_t min_rc = 64 / part_rw;  // rings of at least two 128-B lines
+    const size_t fixed_b = 16 * ((ptotal + 66) & ~1ull) + 4 * 64 * pl.part_rw + 4 * wave_bytes;  // + caps, dummies, cancel
+    const uint64_t min_rc = 64 / pl.part_rw;  // rings of at least two 128-B lines
     for (int per_cu = 2; ok && per_cu >= 1 && !p.pscan; --per_cu) {
       const size_t budget = PGPU_LDS_LIMIT / per_cu;
       if (budget <= fixed_b) continue;
       uint64_t rc = 1;
-      while (rc < 1024 && fixed_b + 4ull * ptotal * part_rw * (rc * 2) <= budget) rc *= 2;
+      while (rc < 1024 && fixed_b + 4ull * ptotal * pl.part_rw * (rc * 2) <= budget) rc *= 2;
       if (rc < min_rc) continue;
       p.pscan = (int32_t)rc;
       p.pscan_wave_bytes = (int32_t)wave_bytes;
       // the widths the prefetching phase 1 is compiled for (part_scan_kernel<false, KB, VB>)
       p.pscan_kb = p.pscan_vb = 0;
-      const bool no_pfetch = getenv("PGPU_NO_PSCAN_PREFETCH") && atoi(getenv("PGPU_NO_PSCAN_PREFETCH")) != 0;
-      if (!no_pfetch && p.ngcols == 1 && pcol >= 0) {
+      if (!env_flag("PGPU_NO_PSCAN_PREFETCH") && p.ngcols == 1 && pl.pcol >= 0) {  // (per plan: tests)
         int kb = -1, vb = -1;
         bool same = true;
         for (const DevSeg& ds : pk.segs) {
           if (!ds.ntiles) continue;
           const DevColumn& kc = pk.cols[ds.col_begin + p.gcols[0]];
-          const DevColumn& vc = pk.cols[ds.col_begin + pcol];
+          const DevColumn& vc = pk.cols[ds.col_begin + pl.pcol];
           same = same && ds.prog_len == 0 && kc.kind == PGPU_COL_FIXED_BIT && vc.kind == PGPU_COL_FIXED_BIT &&
                  (kb < 0 || kb == kc.bits) && (vb < 0 || vb == vc.bits);
           kb = kc.bits;
@@ -3363,90 +3416,177 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
           p.pscan_vb = vb;
         }
       }
-      int g = (int)std::min<int64_t>((int64_t)ctx->num_cus * per_cu, std::max(1, p.total_tiles / 4));
-      if (g >= 8) g &= ~7;
-      p.direct = 0;
-      grid = std::max(1, g);
-      dyn = align16(fixed_b + 4ull * ptotal * part_rw * rc);
+      p.direct = PGPU_KV_RING;
+      pl.grid = stream_grid(num_cus, per_cu, p.total_tiles, 4);
+      pl.dyn = align16(fixed_b + 4ull * ptotal * pl.part_rw * rc);
     }
   }
-  if (ldict == 2 && !p.pscan) {  // the ring's partition counters were sized for the original geometry
-    pshift = for_old_pshift;
-    nparts = for_old_nparts;
-    ldict = 0;
-    for_h = nullptr;
+  if (pl.ldict == 2 && !p.pscan) {
+    pl.pshift = old_pshift;
+    pl.nparts = old_nparts;
+    pl.ldict = 0;
+    pl.for_h = nullptr;
   }
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (!ctx->lds_ready) {
-      HIP_TRY(pgpu_prepare_query_kernels(PGPU_LDS_LIMIT));
-      ctx->lds_ready = true;
-    }
-  }
-  const int nwaves = grid * (p.direct || p.pscan ? 4 : PGPU_WAVES_OF(p.dense));
+}
 
-  static const bool trace = getenv("PGPU_PLAN_TRACE") && atoi(getenv("PGPU_PLAN_TRACE")) != 0;
-  if (trace) {  // diagnostics: the plan of each segment and the kernel chosen
-    fprintf(stderr, "[pgpu plan] mode %d dense %d direct %d pscan %d grid %d dyn %zu tiles %d units %d invx %zu\n",
-            p.mode, p.dense, p.direct, p.pscan, grid, dyn, p.total_tiles, p.total_units, pk.invx.size());
-    for (size_t i = 0; i < pk.segs.size(); ++i) {
-      const DevSeg& ds = pk.segs[i];
-      fprintf(stderr, "[pgpu plan]  seg %zu tiles %d prog %d (op %d) rprog %d agg_mode %d nstage %d fast %d sliced %d "
-              "nvstage %d single_bits %d nbits %d\n", i, ds.ntiles, ds.prog_len,
-              ds.prog_len ? pk.instrs[ds.prog_begin].op : -1, ds.rprog_len, ds.agg_mode, ds.nstage, ds.fast,
-              ds.stage_sliced, ds.nvstage, ds.single_bits, ds.nbits);
-    }
+// PGPU_PLAN_TRACE=1: the kernel chosen and the plan of each segment, on stderr
+void trace_plan(const Packer& pk, const DevParams& p, const LaunchPlan& pl) {
+  fprintf(stderr, "[pgpu plan] mode %d dense %d direct %d pscan %d grid %d dyn %zu tiles %d units %d invx %zu "
+          "rd_planes %d rd_pfx %d rs_vplanes %d dslots %d min_instrs %d ring_slots %d inflight %d rk_ids %d "
+          "rk_leaves %d pscan_kb %d pscan_vb %d pshift %d nparts %llu ldict %d rw %d rec_idbits %d nwaves %d\n",
+          p.mode, p.dense, p.direct, p.pscan, pl.grid, pl.dyn, p.total_tiles, p.total_units, pk.invx.size(),
+          p.rd_planes, p.rd_pfx, p.rs_vplanes, p.dslots, p.min_instrs, p.ring_slots, p.inflight, p.rk_ids,
+          p.rk_leaves, p.pscan_kb, p.pscan_vb, pl.pshift, (unsigned long long)pl.nparts, pl.ldict, pl.part_rw,
+          pl.part_idbits, pl.nwaves);
+  for (size_t i = 0; i < pk.segs.size(); ++i) {
+    const DevSeg& ds = pk.segs[i];
+    fprintf(stderr, "[pgpu plan]  seg %zu tiles %d prog %d (op %d) rprog %d agg_mode %d nstage %d fast %d sliced %d "
+            "nvstage %d single_bits %d nbits %d\n", i, ds.ntiles, ds.prog_len,
+            ds.prog_len ? pk.instrs[ds.prog_begin].op : -1, ds.rprog_len, ds.agg_mode, ds.nstage, ds.fast,
+            ds.stage_sliced, ds.nvstage, ds.single_bits, ds.nbits);
   }
-  const double tw0 = HostTiming::us();
-  Workspace* ws = acquire_ws(ctx, &rc);
-  if (!ws) return rc;
-  hipStream_t bail_stream = nullptr;
-  auto bail = [&](int code) {
-    // a bail after the query kernel was enqueued but before finalize_kernel: the matched-segment words it may
-    // have set must not count towards the workspace's next query (they are zero between queries)
-    if (bail_stream && ws->segany.p) (void)hipMemsetAsync(ws->segany.p, 0, ws->segany.n, bail_stream);
-    if (bail_stream && ws->ticket.p) (void)hipMemsetAsync(ws->ticket.p, 0, ws->ticket.n, bail_stream);
-    release_ws(ctx, ws);
-    return code;
-  };
-  // NULL stream: the context's query stream (queries run back to back; each has its own completion event).  The
-  // cancel stream is created here too, never in pgpu_query_cancel (stream creation may wait for the device).
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (!stream && !ctx->qstream) {
-      const hipError_t ce = hipStreamCreateWithFlags(&ctx->qstream, hipStreamNonBlocking);
-      if (ce != hipSuccess) return bail(fail(PGPU_E_HIP, "query stream: %s", hipGetErrorString(ce)));
-    }
-    if (!ctx->cstream) {
-      const hipError_t ce = hipStreamCreateWithFlags(&ctx->cstream, hipStreamNonBlocking);
-      if (ce != hipSuccess) return bail(fail(PGPU_E_HIP, "cancel stream: %s", hipGetErrorString(ce)));
-    }
-  }
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->qstream;
-  bail_stream = st;
+}
 
-  // arena: segs | instrs | cols | pool | remaps
-  const size_t o_segs = 0;
-  const size_t o_ins = align16(o_segs + pk.segs.size() * sizeof(DevSeg));
-  const size_t o_cols = align16(o_ins + pk.instrs.size() * sizeof(DevInstr));
-  const size_t o_pool = align16(o_cols + pk.cols.size() * sizeof(DevColumn));
-  const size_t o_rem = align16(o_pool + pk.pool.size() * 4);
-  const size_t o_raw = align16(o_rem + pk.remaps.size() * sizeof(void*));
-  const size_t o_rvals = align16(o_raw + pk.raws.size() * sizeof(RawLeaf));
-  const size_t o_mv = align16(o_rvals + pk.rawvals.size() * 8);
-  const size_t o_mvset = align16(o_mv + pk.mvs.size() * sizeof(MvLeaf));
-  const size_t o_inv = align16(o_mvset + pk.mvsets.size() * 4);
-  const size_t o_invids = align16(o_inv + pk.invx.size() * sizeof(InvLeafX));
-  const size_t o_jobs = align16(o_invids + pk.invids.size() * 4);
-  const size_t o_cand = align16(o_jobs + pk.jobs.size() * sizeof(ProgJob));
-  const size_t total = align16(o_cand + pk.cand.size() * 4) + 16;
-  hipError_t e = ws->h_arena.ensure(total);
+bool plan_trace_on() {
+  static const bool trace = env_flag("PGPU_PLAN_TRACE");
+  return trace;
+}
+
+// Which kernel the query gets, with which grid, LDS size and template widths.  No HIP call.  The order of the
+// calls is the behaviour: each variant is tried only from the variant named in its condition and overrides it.
+int plan_launch(int num_cus, const pgpu_query_desc* q, const pgpu_table_layout& L, Packer& pk, DevParams& p,
+                LaunchPlan& pl) {
+  const int rc = plan_mode_and_ring(num_cus, q, L, pk, p, pl);  // ring: the default
+  if (rc) return rc;
+  if (self_loading_ok(pk, p)) {
+    try_direct(num_cus, pk, p, pl);   // ring -> direct
+    try_rdirect(num_cus, pk, p, pl);  // ring or direct -> rdirect
+    try_rstream(num_cus, pk, p, pl);  // any of them -> rstream
+  }
+  try_rprog(num_cus, pk, p, pl);      // direct -> rprog -> rkey
+  try_cand(num_cus, q, pk, p, pl);    // direct -> cand
+  try_rfsm(num_cus, pk, p, pl);       // rdirect -> rfsm
+  demote_sliced_agg(pk, p);           // after every variant above: only direct, rstream and rprog keep SLICED
+  plan_part_records(q, L, p, pl);
+  try_pscan(num_cus, q, L, pk, p, pl);  // PART: any -> ring + pscan (PGPU_KV_PSCAN), with the FOR geometry
+  pl.nwaves = pl.grid * (p.direct != PGPU_KV_RING || p.pscan ? 4 : PGPU_WAVES_OF(p.dense));
+  if (plan_trace_on()) trace_plan(pk, p, pl);
+  return PGPU_OK;
+}
+
+// The query's stream.  NULL: the context's query stream (queries run back to back; each has its own completion
+// event).  The cancel stream is created here too, never in pgpu_query_cancel (stream creation may wait for the
+// device).
+int query_stream(pgpu_context* ctx, void* stream, hipStream_t* out) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!stream && !ctx->qstream) {
+    const hipError_t ce = hipStreamCreateWithFlags(&ctx->qstream, hipStreamNonBlocking);
+    if (ce != hipSuccess) return fail(PGPU_E_HIP, "query stream: %s", hipGetErrorString(ce));
+  }
+  if (!ctx->cstream) {
+    const hipError_t ce = hipStreamCreateWithFlags(&ctx->cstream, hipStreamNonBlocking);
+    if (ce != hipSuccess) return fail(PGPU_E_HIP, "cancel stream: %s", hipGetErrorString(ce));
+  }
+  *out = stream ? (hipStream_t)stream : ctx->qstream;
+  return PGPU_OK;
+}
+
+// The metadata arena: one host image of 13 sections (each 16-byte aligned) that the prologue copies to the device
+struct ArenaLayout {
+  size_t segs, ins, cols, pool, rem, raw, rvals, mv, mvset, inv, invids, jobs, cand, total;
+};
+ArenaLayout arena_layout(const Packer& pk) {
+  ArenaLayout A;
+  A.segs = 0;
+  A.ins = align16(A.segs + pk.segs.size() * sizeof(DevSeg));
+  A.cols = align16(A.ins + pk.instrs.size() * sizeof(DevInstr));
+  A.pool = align16(A.cols + pk.cols.size() * sizeof(DevColumn));
+  A.rem = align16(A.pool + pk.pool.size() * 4);
+  A.raw = align16(A.rem + pk.remaps.size() * sizeof(void*));
+  A.rvals = align16(A.raw + pk.raws.size() * sizeof(RawLeaf));
+  A.mv = align16(A.rvals + pk.rawvals.size() * 8);
+  A.mvset = align16(A.mv + pk.mvs.size() * sizeof(MvLeaf));
+  A.inv = align16(A.mvset + pk.mvsets.size() * 4);
+  A.invids = align16(A.inv + pk.invx.size() * sizeof(InvLeafX));
+  A.jobs = align16(A.invids + pk.invids.size() * 4);
+  A.cand = align16(A.jobs + pk.jobs.size() * sizeof(ProgJob));
+  A.total = align16(A.cand + pk.cand.size() * 4) + 16;
+  return A;
+}
+
+// PART record buffers and the geometry the kernels read.  Region capacity: 1.25x the expected records per
+// (partition, workgroup) + slack; full regions spill to HBM atomics, so an underestimate costs time, never
+// correctness.  Bounded by half the free HBM.
+hipError_t ensure_part_records(pgpu_context* ctx, const pgpu_query_desc* q, const Packer& pk, const LaunchPlan& pl,
+                               Workspace* ws, hipStream_t st, DevParams& p) {
+  p.pshift = pl.pshift;
+  p.nparts = (int32_t)pl.nparts;
+  p.slice_shift = pl.slice_shift;
+  p.ldict = pl.ldict;
+  p.pdict_n = pl.pdict_n;
+  p.pfor = pl.for_h ? (const uint32_t*)pl.for_h->for_dev.p : nullptr;
+  p.for_bits = pl.for_h ? pl.for_h->for_bits : 0;
+  p.for_nblk = pl.for_h ? pl.for_h->for_nblk : 0;
+  p.pcol = pl.pcol;
+  p.rw = pl.part_rw;
+  p.rec_idbits = pl.part_idbits;
+  p.pdict = pl.part_pdict;
+  const double per = pk.est_matched / ((double)pl.grid * (double)p.nparts);
+  uint64_t cap = (uint64_t)(1.25 * per) + 32;
+  if (q->flags & PGPU_Q_PART_SPILL) cap = 16;
+  // regions of an odd number of 128-B lines: the active (partially written) line of every region then falls on
+  // a different L2 set instead of all regions' cursors sharing a few sets, so lines stay resident until full
+  const uint64_t per_line = 32 / p.rw;
+  uint64_t lines = (cap + per_line - 1) / per_line;
+  if (!(q->flags & PGPU_Q_PART_SPILL) && (lines & 1) == 0) ++lines;
+  cap = lines * per_line;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+  const uint64_t regions = (uint64_t)p.nparts * (uint64_t)pl.grid;
+  const uint64_t have = ws->recs.n;
+  const uint64_t budget = std::max<uint64_t>(have, (uint64_t)free_b / 2);
+  const uint64_t max_cap = budget / (regions * 4ull * p.rw);
+  if (cap > max_cap) cap = max_cap / per_line * per_line;
+  if (cap > (uint64_t)INT32_MAX) cap = (uint64_t)INT32_MAX / per_line * per_line;
+  p.rcap = (int32_t)std::max<uint64_t>(cap, 16);
+  hipError_t e = ws->recs.ensure(regions * (uint64_t)p.rcap * 4ull * p.rw, ctx->mpool, st);
+  if (e == hipSuccess) e = ws->rcount.ensure(4ull * regions, ctx->mpool, st);
+  p.pblock = (uint64_t)p.nparts * (uint64_t)p.rcap;  // records per phase-1 workgroup block
+  p.pcount = p.pcap = p.poff = nullptr;
+  p.p2work = nullptr;
+  p.p2grid = p.nparts;
+  static const bool no_psize = env_flag("PGPU_NO_PSIZE");
+  if (p.pscan && !no_psize && !(q->flags & PGPU_Q_PART_SPILL)) {
+    // regions sized from a sampled count (~8K tiles) and heavy partitions split in phase 2: skewed keys
+    // (Zipf) would otherwise overflow their regions into HBM atomics and leave one phase-2 workgroup with most
+    // of the records
+    p.psample = std::max(1, p.total_tiles / 8192);
+    p.p2grid = 2 * p.nparts;
+    if (e == hipSuccess) e = ws->pcount.ensure(4ull * p.nparts, ctx->mpool, st);
+    if (e == hipSuccess) e = ws->pcap.ensure(4ull * p.nparts, ctx->mpool, st);
+    if (e == hipSuccess) e = ws->poff.ensure(4ull * p.nparts, ctx->mpool, st);
+    if (e == hipSuccess) e = ws->p2work.ensure(16ull * p.p2grid, ctx->mpool, st);
+    p.pcount = (uint32_t*)ws->pcount.p;
+    p.pcap = (uint32_t*)ws->pcap.p;
+    p.poff = (uint32_t*)ws->poff.p;
+    p.p2work = (int32_t*)ws->p2work.p;
+  }
+  p.recs = (uint32_t*)ws->recs.p;
+  p.rcount = (uint32_t*)ws->rcount.p;
+  return e;
+}
+
+// Grow the workspace's buffers to this query's sizes (stream-ordered, from the context's pool) and point DevParams
+// at the ones only some queries use
+int ensure_workspace(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_layout& L, const Packer& pk,
+                     const LaunchPlan& pl, size_t arena_bytes, Workspace* ws, hipStream_t st, DevParams& p) {
+  hipError_t e = ws->h_arena.ensure(arena_bytes);
   const void* arena_p0 = ws->arena.p;
   const size_t arena_n0 = ws->arena.n;
-  if (e == hipSuccess) e = ws->arena.ensure(total, ctx->mpool, st);
+  if (e == hipSuccess) e = ws->arena.ensure(arena_bytes, ctx->mpool, st);
   if (ws->arena.p != arena_p0 || ws->arena.n != arena_n0) ws->arena_shadow.clear();
-  if (e == hipSuccess) e = ws->slab.ensure(8ull * nwaves * L.num_sections + 16, ctx->mpool, st);
-  if (e == hipSuccess) e = ws->stats.ensure(8ull * nwaves * PGPU_NSTATS + 16, ctx->mpool, st);
+  if (e == hipSuccess) e = ws->slab.ensure(8ull * pl.nwaves * L.num_sections + 16, ctx->mpool, st);
+  if (e == hipSuccess) e = ws->stats.ensure(8ull * pl.nwaves * PGPU_NSTATS + 16, ctx->mpool, st);
   if (e == hipSuccess) e = ws->stats_out.ensure(8 * PGPU_NSTATS, ctx->mpool, st);
   if (e == hipSuccess) e = ws->h_stats.ensure(8 * PGPU_NSTATS + 16);
   // the cancel copy's pinned source is allocated here, never in pgpu_query_cancel: an allocation there could wait
@@ -3463,88 +3603,33 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
       ws->d_cancel.p = nullptr;
     }
   }
-  if (e == hipSuccess && (p.flags & PGPU_FLAG_PROFILE)) e = ws->prof.ensure(8ull * nwaves * PGPU_NPROF, ctx->mpool, st);
-  if (e != hipSuccess) return bail(fail(PGPU_E_HIP, "workspace allocation: %s", hipGetErrorString(e)));
+  if (e == hipSuccess && (p.flags & PGPU_FLAG_PROFILE)) e = ws->prof.ensure(8ull * pl.nwaves * PGPU_NPROF, ctx->mpool, st);
+  if (e != hipSuccess) return fail(PGPU_E_HIP, "workspace allocation: %s", hipGetErrorString(e));
   if (p.mode == PGPU_MODE_PART) {
-    // region capacity: 1.25x the expected records per (partition, workgroup) + slack; full regions spill to
-    // HBM atomics, so an underestimate costs time, never correctness.  Bounded by half the free HBM.
-    p.pshift = pshift;
-    p.nparts = (int32_t)nparts;
-    p.slice_shift = slice_shift;
-    p.ldict = ldict;
-    p.pdict_n = pdict_n;
-    p.pfor = for_h ? (const uint32_t*)for_h->for_dev.p : nullptr;
-    p.for_bits = for_h ? for_h->for_bits : 0;
-    p.for_nblk = for_h ? for_h->for_nblk : 0;
-    p.pcol = pcol;
-    p.rw = part_rw;
-    p.rec_idbits = part_idbits;
-    p.pdict = part_pdict;
-    const double per = pk.est_matched / ((double)grid * (double)p.nparts);
-    uint64_t cap = (uint64_t)(1.25 * per) + 32;
-    if (q->flags & PGPU_Q_PART_SPILL) cap = 16;
-    // regions of an odd number of 128-B lines: the active (partially written) line of every region then falls on
-    // a different L2 set instead of all regions' cursors sharing a few sets, so lines stay resident until full
-    const uint64_t per_line = 32 / p.rw;
-    uint64_t lines = (cap + per_line - 1) / per_line;
-    if (!(q->flags & PGPU_Q_PART_SPILL) && (lines & 1) == 0) ++lines;
-    cap = lines * per_line;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-    const uint64_t regions = (uint64_t)p.nparts * (uint64_t)grid;
-    const uint64_t have = ws->recs.n;
-    const uint64_t budget = std::max<uint64_t>(have, (uint64_t)free_b / 2);
-    const uint64_t max_cap = budget / (regions * 4ull * p.rw);
-    if (cap > max_cap) cap = max_cap / per_line * per_line;
-    if (cap > (uint64_t)INT32_MAX) cap = (uint64_t)INT32_MAX / per_line * per_line;
-    p.rcap = (int32_t)std::max<uint64_t>(cap, 16);
-    e = ws->recs.ensure(regions * (uint64_t)p.rcap * 4ull * p.rw, ctx->mpool, st);
-    if (e == hipSuccess) e = ws->rcount.ensure(4ull * regions, ctx->mpool, st);
-    p.pblock = (uint64_t)p.nparts * (uint64_t)p.rcap;  // records per phase-1 workgroup block
-    p.pcount = p.pcap = p.poff = nullptr;
-    p.p2work = nullptr;
-    p.p2grid = p.nparts;
-    static const bool no_psize = getenv("PGPU_NO_PSIZE") && atoi(getenv("PGPU_NO_PSIZE")) != 0;
-    if (p.pscan && !no_psize && !(q->flags & PGPU_Q_PART_SPILL)) {
-      // regions sized from a sampled count (~8K tiles) and heavy partitions split in phase 2: skewed keys
-      // (Zipf) would otherwise overflow their regions into HBM atomics and leave one phase-2 workgroup with most
-      // of the records
-      p.psample = std::max(1, p.total_tiles / 8192);
-      p.p2grid = 2 * p.nparts;
-      if (e == hipSuccess) e = ws->pcount.ensure(4ull * p.nparts, ctx->mpool, st);
-      if (e == hipSuccess) e = ws->pcap.ensure(4ull * p.nparts, ctx->mpool, st);
-      if (e == hipSuccess) e = ws->poff.ensure(4ull * p.nparts, ctx->mpool, st);
-      if (e == hipSuccess) e = ws->p2work.ensure(16ull * p.p2grid, ctx->mpool, st);
-      p.pcount = (uint32_t*)ws->pcount.p;
-      p.pcap = (uint32_t*)ws->pcap.p;
-      p.poff = (uint32_t*)ws->poff.p;
-      p.p2work = (int32_t*)ws->p2work.p;
-    }
-    if (e != hipSuccess) return bail(fail(PGPU_E_HIP, "group-by record buffers: %s", hipGetErrorString(e)));
-    p.recs = (uint32_t*)ws->recs.p;
-    p.rcount = (uint32_t*)ws->rcount.p;
+    e = ensure_part_records(ctx, q, pk, pl, ws, st, p);
+    if (e != hipSuccess) return fail(PGPU_E_HIP, "group-by record buffers: %s", hipGetErrorString(e));
   }
-  if (pk.raw_words > 0 && p.direct != 5) {  // (query_kernel_rkey builds its leaf images in LDS)
+  if (pk.raw_words > 0 && p.direct != PGPU_KV_RKEY) {  // (query_kernel_rkey builds its leaf images in LDS)
     e = ws->rawbits.ensure(4ull * pk.raw_words, ctx->mpool, st);
-    if (e != hipSuccess) return bail(fail(PGPU_E_HIP, "raw-value leaf bitmaps: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(PGPU_E_HIP, "raw-value leaf bitmaps: %s", hipGetErrorString(e));
   }
   p.rk_ctab = nullptr;
-  if (p.direct == 5) {
+  if (p.direct == PGPU_KV_RKEY) {
     e = ws->rkctab.ensure(sizeof(DevContainer) * (size_t)std::max<int64_t>(1, pk.rk_ctab_records), ctx->mpool, st);
-    if (e != hipSuccess) return bail(fail(PGPU_E_HIP, "container table: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(PGPU_E_HIP, "container table: %s", hipGetErrorString(e));
     p.rk_ctab = (const DevContainer*)ws->rkctab.p;
   }
   p.fsm_fn = nullptr;
   if (pk.fsm) {
     e = ws->fsmfn.ensure(32ull * std::max(1, p.total_tiles), ctx->mpool, st);
     if (e == hipSuccess) e = ws->h_fsment.ensure(8ull * std::max(1, p.nseg));
-    if (e != hipSuccess) return bail(fail(PGPU_E_HIP, "filter-statistics maps: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(PGPU_E_HIP, "filter-statistics maps: %s", hipGetErrorString(e));
     p.fsm_fn = (uint32_t*)ws->fsmfn.p;
   }
   if (pk.leaf_words > 0) {
     e = ws->leafbits.ensure(4ull * pk.leaf_words, ctx->mpool, st);
     if (e == hipSuccess) e = ws->h_leafbits.ensure(4ull * pk.leaf_words);
-    if (e != hipSuccess) return bail(fail(PGPU_E_HIP, "filter-statistics bitmaps: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(PGPU_E_HIP, "filter-statistics bitmaps: %s", hipGetErrorString(e));
     p.leaf_bits = (uint32_t*)ws->leafbits.p;
   }
   {
@@ -3555,7 +3640,7 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
       if (e == hipSuccess) e = hipMemsetAsync(ws->segany.p, 0, ws->segany.n, st);
     }
     if (e == hipSuccess) e = ws->h_segany.ensure((size_t)std::max(1, p.nseg));
-    if (e != hipSuccess) return bail(fail(PGPU_E_HIP, "segment match words: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(PGPU_E_HIP, "segment match words: %s", hipGetErrorString(e));
     p.segany = (uint32_t*)ws->segany.p;
   }
   if (p.mode == PGPU_MODE_HASH) {
@@ -3564,220 +3649,274 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
     if (e == hipSuccess && p.segmask_rows) e = ws->segmask.ensure((size_t)p.segmask_rows * (L.num_keys / 8) + 16, ctx->mpool, st);
     if (e == hipSuccess && p.segmask_rows) e = ws->h_segcnt.ensure(8 * (size_t)p.segmask_rows);
     if (e == hipSuccess) e = hipMemsetAsync(ws->hflag.p, 0, 16, st);
-    if (e != hipSuccess) return bail(fail(PGPU_E_HIP, "hash group-by buffers: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(PGPU_E_HIP, "hash group-by buffers: %s", hipGetErrorString(e));
     p.hflag = (int32_t*)ws->hflag.p;
     p.segmask = p.segmask_rows ? (uint32_t*)ws->segmask.p : nullptr;
   }
+  return PGPU_OK;
+}
+
+// Longest bitmap (32-bit words) of each kind of leaf a kernel expands before the query kernel: its grid
+struct LeafWords {
+  int64_t raw = 0, mv = 0, inv = 0;
+};
+
+// Turn the packer's offsets into device pointers (bitmaps in the workspace, everything else in the arena), write the
+// arena's host image and point DevParams at its sections
+LeafWords fill_arena(Packer& pk, const ArenaLayout& A, Workspace* ws, const void* dev_table, DevParams& p) {
   char* h = (char*)ws->h_arena.p;
   char* d = (char*)ws->arena.p;
-  // raw-value leaves: offsets -> device pointers (bitmaps in the workspace, set values in the arena)
-  for (int idx : pk.bits_instrs)
-    pk.instrs[idx].fwd = (const uint32_t*)ws->rawbits.p + (intptr_t)pk.instrs[idx].fwd;
+  const uint32_t* rawbits = (const uint32_t*)ws->rawbits.p;
+  LeafWords w;
+  for (int idx : pk.bits_instrs) pk.instrs[idx].fwd = rawbits + (intptr_t)pk.instrs[idx].fwd;
   for (DevSeg& sg : pk.segs)
-    for (int k = 0; k < sg.nbits; ++k) sg.bits_w[k] = (const uint32_t*)ws->rawbits.p + (intptr_t)sg.bits_w[k];
-  int64_t max_raw_words = 0;
+    for (int k = 0; k < sg.nbits; ++k) sg.bits_w[k] = rawbits + (intptr_t)sg.bits_w[k];
   for (RawLeaf& r : pk.raws) {
-    r.out = (uint32_t*)ws->rawbits.p + (intptr_t)r.out;
-    r.vals = (const int64_t*)(d + o_rvals) + (intptr_t)r.vals;
-    max_raw_words = std::max<int64_t>(max_raw_words, r.words);
+    r.out = (uint32_t*)rawbits + (intptr_t)r.out;
+    r.vals = (const int64_t*)(d + A.rvals) + (intptr_t)r.vals;
+    w.raw = std::max<int64_t>(w.raw, r.words);
   }
-  int64_t max_mv_words = 0;
   for (MvLeaf& m : pk.mvs) {
-    m.out = (uint32_t*)ws->rawbits.p + (intptr_t)m.out;
-    m.set = m.set ? (const uint32_t*)(d + o_mvset) + ((intptr_t)m.set - 1) : nullptr;
-    max_mv_words = std::max<int64_t>(max_mv_words, m.words);
+    m.out = (uint32_t*)rawbits + (intptr_t)m.out;
+    m.set = m.set ? (const uint32_t*)(d + A.mvset) + ((intptr_t)m.set - 1) : nullptr;
+    w.mv = std::max<int64_t>(w.mv, m.words);
   }
-  memcpy(h + o_mv, pk.mvs.data(), pk.mvs.size() * sizeof(MvLeaf));
-  int64_t max_inv_words = 0;
   for (InvLeafX& x : pk.invx) {
-    x.out = (uint32_t*)ws->rawbits.p + (intptr_t)x.out;
-    x.ids = (const int32_t*)(d + o_invids) + (intptr_t)x.ids;
-    max_inv_words = std::max<int64_t>(max_inv_words, x.words);
+    x.out = (uint32_t*)rawbits + (intptr_t)x.out;
+    x.ids = (const int32_t*)(d + A.invids) + (intptr_t)x.ids;
+    w.inv = std::max<int64_t>(w.inv, x.words);
   }
-  memcpy(h + o_inv, pk.invx.data(), pk.invx.size() * sizeof(InvLeafX));
   for (ProgJob& jb : pk.jobs) {
-    jb.out = (uint32_t*)ws->rawbits.p + (intptr_t)jb.out;
-    for (int k = 0; k < jb.nbits; ++k) jb.bits_w[k] = (const uint32_t*)ws->rawbits.p + (intptr_t)jb.bits_w[k];
+    jb.out = (uint32_t*)rawbits + (intptr_t)jb.out;
+    for (int k = 0; k < jb.nbits; ++k) jb.bits_w[k] = rawbits + (intptr_t)jb.bits_w[k];
   }
-  memcpy(h + o_jobs, pk.jobs.data(), pk.jobs.size() * sizeof(ProgJob));
-  memcpy(h + o_cand, pk.cand.data(), pk.cand.size() * 4);
-  p.cand_ct = (const uint32_t*)(d + o_cand);
-  memcpy(h + o_invids, pk.invids.data(), pk.invids.size() * 4);
-  memcpy(h + o_mvset, pk.mvsets.data(), pk.mvsets.size() * 4);
-  memcpy(h + o_raw, pk.raws.data(), pk.raws.size() * sizeof(RawLeaf));
-  memcpy(h + o_rvals, pk.rawvals.data(), pk.rawvals.size() * 8);
-  memcpy(h + o_segs, pk.segs.data(), pk.segs.size() * sizeof(DevSeg));
-  memcpy(h + o_ins, pk.instrs.data(), pk.instrs.size() * sizeof(DevInstr));
-  memcpy(h + o_cols, pk.cols.data(), pk.cols.size() * sizeof(DevColumn));
-  memcpy(h + o_pool, pk.pool.data(), pk.pool.size() * 4);
-  memcpy(h + o_rem, pk.remaps.data(), pk.remaps.size() * sizeof(void*));
-  const double tl0 = HostTiming::us();
-  host_timing().add(3, tw0, tl0);
-  p.segs = (const DevSeg*)(d + o_segs);
-  p.instrs = (const DevInstr*)(d + o_ins);
-  p.cols = (const DevColumn*)(d + o_cols);
-  p.pool = (const int32_t*)(d + o_pool);
-  p.remaps = (const int32_t* const*)(d + o_rem);
+  memcpy(h + A.mv, pk.mvs.data(), pk.mvs.size() * sizeof(MvLeaf));
+  memcpy(h + A.inv, pk.invx.data(), pk.invx.size() * sizeof(InvLeafX));
+  memcpy(h + A.jobs, pk.jobs.data(), pk.jobs.size() * sizeof(ProgJob));
+  memcpy(h + A.cand, pk.cand.data(), pk.cand.size() * 4);
+  memcpy(h + A.invids, pk.invids.data(), pk.invids.size() * 4);
+  memcpy(h + A.mvset, pk.mvsets.data(), pk.mvsets.size() * 4);
+  memcpy(h + A.raw, pk.raws.data(), pk.raws.size() * sizeof(RawLeaf));
+  memcpy(h + A.rvals, pk.rawvals.data(), pk.rawvals.size() * 8);
+  memcpy(h + A.segs, pk.segs.data(), pk.segs.size() * sizeof(DevSeg));
+  memcpy(h + A.ins, pk.instrs.data(), pk.instrs.size() * sizeof(DevInstr));
+  memcpy(h + A.cols, pk.cols.data(), pk.cols.size() * sizeof(DevColumn));
+  memcpy(h + A.pool, pk.pool.data(), pk.pool.size() * 4);
+  memcpy(h + A.rem, pk.remaps.data(), pk.remaps.size() * sizeof(void*));
+  p.segs = (const DevSeg*)(d + A.segs);
+  p.instrs = (const DevInstr*)(d + A.ins);
+  p.cols = (const DevColumn*)(d + A.cols);
+  p.pool = (const int32_t*)(d + A.pool);
+  p.remaps = (const int32_t* const*)(d + A.rem);
+  p.invx = (const InvLeafX*)(d + A.inv);
+  p.cand_ct = (const uint32_t*)(d + A.cand);
   p.table = (int64_t*)dev_table;
   p.slab = (int64_t*)ws->slab.p;
   p.stats = (int64_t*)ws->stats.p;
   p.prof = (int64_t*)ws->prof.p;
+  return w;
+}
 
-  // metadata in and stats (and small tables) out through pinned host memory touched by kernels: no DMA-engine
-  // copy sits between two queries' kernels
-  void* h_arena_dev = nullptr;
-  void* h_stats_dev = nullptr;
-  // cancel word in HBM: a query is stopped when the word equals its generation (no reset that could race a
-  // cancel issued from another stream); the kernels poll it with uncached loads
+// Cancel word in HBM: a query is stopped when the word equals its generation (no reset that could race a cancel
+// issued from another stream); the kernels poll it with uncached loads.  A query already past its deadline is
+// cancelled before it starts (*expired).
+hipError_t arm_cancel(const pgpu_query_desc* q, Workspace* ws, hipStream_t st, DevParams& p, bool* expired) {
   if (++ws->cancel_gen == 0) ws->cancel_gen = 1;
   p.cancel = (const int32_t*)ws->d_cancel.p;
   p.cancel_gen = ws->cancel_gen;
-  const bool expired = q->deadline_ms > 0 && now_epoch_ms() >= q->deadline_ms;
-  if (expired) e = hipMemsetD32Async((hipDeviceptr_t)ws->d_cancel.p, (int)ws->cancel_gen, 1, st);
-  if (e == hipSuccess) e = ws->h_arena.device_ptr(&h_arena_dev);
-  if (e == hipSuccess) e = ws->h_stats.device_ptr(&h_stats_dev);
-  p.invx = (const InvLeafX*)(d + o_inv);
-  bool expand = false;  // (query_kernel_rkey and query_kernel_cand read their leaves' containers themselves)
+  *expired = q->deadline_ms > 0 && now_epoch_ms() >= q->deadline_ms;
+  return *expired ? hipMemsetD32Async((hipDeviceptr_t)ws->d_cancel.p, (int)ws->cancel_gen, 1, st) : hipSuccess;
+}
+
+// Where the caller wants the table (launch_impl's arguments)
+struct TableTarget {
+  void* dev_table;
+  int64_t* host_table;  // device-visible pointer into pinned host memory, or null: the finished table is also exported there
+  bool eager;
+  const pgpu_topk* eager_order;
+  Workspace* tws;  // the workspace owning dev_table, or null (caller's own table or stream)
+};
+
+// (query_kernel_rkey and query_kernel_cand read their leaves' containers themselves)
+bool any_leaf_expanded(const Packer& pk) {
+  bool expand = false;
   for (const InvLeafX& x : pk.invx) expand |= !x.skip;
-  // One launch instead of three (prologue, query kernel, finalize): a submitted register-direct query with a small
-  // table and no kernel before or behind the query kernel.  Its last workgroup does finalize_kernel's work
-  // (fused_finalize); the arena is copied only when its bytes differ from what the device holds; a table that
-  // needs identities is the workspace's spare table when the previous fused query prepared it for this layout.
-  // PGPU_Q_SPLIT_LAUNCH (PGPU_SPLIT_LAUNCH=1: every query) keeps the three launches.
-  static const bool env_split = getenv("PGPU_SPLIT_LAUNCH") && atoi(getenv("PGPU_SPLIT_LAUNCH")) != 0;
+  return expand;
+}
+
+// Why the query keeps the three launches (prologue, query kernels, finalize), or null: it runs as one.  One launch:
+// a submitted register-direct query with a small table and no kernel before or behind the query kernel.
+// PGPU_Q_SPLIT_LAUNCH (PGPU_SPLIT_LAUNCH=1: every query) keeps the three launches.
+const char* split_reason(const pgpu_query_desc* q, const pgpu_table_layout& L, const Packer& pk, const DevParams& p,
+                         const LaunchPlan& pl, const TableTarget& t) {
+  static const bool env_split = env_flag("PGPU_SPLIT_LAUNCH");
   const uint64_t table_words = pgpu_table_bytes(&L) / 8;
-  const char* split_why = nullptr;  // why the query keeps the three launches (PGPU_PLAN_TRACE)
-  if (!tws) split_why = "external stream or table";
-  else if (env_split || (q->flags & PGPU_Q_SPLIT_LAUNCH)) split_why = "forced";
-  else if (!host_table || eager || (q->flags & PGPU_Q_FOLD)) split_why = "table not exported whole";
-  else if (p.direct != 2 || p.pscan ||
-           !(p.mode == PGPU_MODE_AGG || p.mode == PGPU_MODE_LDS || p.mode == PGPU_MODE_GLOBAL))
-    split_why = "not a register-direct AGG / LDS / GLOBAL query";
-  else if (pk.fsm || pk.leaf_words > 0 || !pk.raws.empty() || !pk.mvs.empty() || expand || !pk.jobs.empty())
-    split_why = "kernels before or behind the query kernel";
-  else if (dyn < PGPU_FUSE_LDS_BYTES || table_words != (uint64_t)p.nsec * p.G ||
-           table_words > PGPU_FUSE_MAX_TABLE_WORDS)
-    split_why = "table too large for one workgroup's epilogue";
-  const bool fuse = split_why == nullptr;
-  bool kernel_is_done = false;  // the query kernel's own end event also says the query is complete
-  if (fuse) {
-    if (e == hipSuccess && !ws->ticket.p) {
-      e = ws->ticket.ensure(16, ctx->mpool, st);
-      if (e == hipSuccess) e = hipMemsetAsync(ws->ticket.p, 0, ws->ticket.n, st);
+  if (!t.tws) return "external stream or table";
+  if (env_split || (q->flags & PGPU_Q_SPLIT_LAUNCH)) return "forced";
+  if (!t.host_table || t.eager || (q->flags & PGPU_Q_FOLD)) return "table not exported whole";
+  if (p.direct != PGPU_KV_RDIRECT || p.pscan ||
+      !(p.mode == PGPU_MODE_AGG || p.mode == PGPU_MODE_LDS || p.mode == PGPU_MODE_GLOBAL))
+    return "not a register-direct AGG / LDS / GLOBAL query";
+  if (pk.fsm || pk.leaf_words > 0 || !pk.raws.empty() || !pk.mvs.empty() || any_leaf_expanded(pk) || !pk.jobs.empty())
+    return "kernels before or behind the query kernel";
+  if (pl.dyn < PGPU_FUSE_LDS_BYTES || table_words != (uint64_t)p.nsec * p.G || table_words > PGPU_FUSE_MAX_TABLE_WORDS)
+    return "table too large for one workgroup's epilogue";
+  return nullptr;
+}
+
+int launch_status(hipError_t e) {
+  return e == hipSuccess ? PGPU_OK : fail(PGPU_E_HIP, "query launch: %s", hipGetErrorString(e));
+}
+
+// One launch instead of three: the query kernel's last workgroup does finalize_kernel's work (fused_finalize); the
+// arena is copied only when its bytes differ from what the device holds; a table that needs identities is the
+// workspace's spare table when the previous fused query prepared it for this layout.  *kernel_is_done: the query
+// kernel's own end event (ev1) also says the query is complete.
+int enqueue_fused(pgpu_context* ctx, const pgpu_table_layout& L, const LaunchPlan& pl, size_t arena_bytes,
+                  const TableTarget& t, Workspace* ws, hipStream_t st, DevParams& p, bool* kernel_is_done) {
+  Workspace* tws = t.tws;
+  const uint64_t need = pgpu_table_bytes(&L);
+  void *h_arena_dev = nullptr, *h_stats_dev = nullptr, *h_seg_dev = nullptr;
+  hipError_t e = ws->h_arena.device_ptr(&h_arena_dev);
+  if (e == hipSuccess) e = ws->h_stats.device_ptr(&h_stats_dev);
+  if (e == hipSuccess && !ws->ticket.p) {
+    e = ws->ticket.ensure(16, ctx->mpool, st);
+    if (e == hipSuccess) e = hipMemsetAsync(ws->ticket.p, 0, ws->ticket.n, st);
+  }
+  if (e == hipSuccess) e = ws->h_segany.device_ptr(&h_seg_dev);
+  bool init_table = p.mode != PGPU_MODE_AGG, spare_hit = false;
+  if (e == hipSuccess && init_table) {
+    Workspace::SpareSig& sg = tws->spare_sig;
+    spare_hit = sg.valid && tws->spare.n >= need && sg.G == p.G && sg.nsec == p.nsec && sg.mode == p.mode &&
+                memcmp(sg.ops, p.sec_op, sizeof(int32_t) * p.nsec) == 0;
+    if (spare_hit) {
+      std::swap(tws->table, tws->spare);
+      p.table = (int64_t*)tws->table.p;
+      init_table = false;
     }
+    sg.valid = false;  // (until this query's kernel is enqueued: it writes the spare)
+    e = tws->spare.ensure(need, ctx->mpool, st);
+    p.fuse_spare = (int64_t*)tws->spare.p;
+  }
+  const char* h = (const char*)ws->h_arena.p;
+  const bool copy = ws->arena_shadow.size() != arena_bytes || memcmp(ws->arena_shadow.data(), h, arena_bytes) != 0;
+  if (copy) ws->arena_shadow.assign(h, h + arena_bytes);
+  p.fuse = 1;
+  p.fuse_nslabs = pl.nwaves;
+  p.fuse_ticket = (uint32_t*)ws->ticket.p;
+  p.fuse_stats_out = (int64_t*)h_stats_dev;
+  p.fuse_seg_out = (uint8_t*)h_seg_dev;
+  p.fuse_host_table = t.host_table;
+  p.fuse_table_words = p.mode != PGPU_MODE_AGG ? need / 8 : 0;
+  if (plan_trace_on())
+    fprintf(stderr, "[pgpu plan] launch fused: arena %s, table %s\n", copy ? "copied" : "resident",
+            p.mode == PGPU_MODE_AGG ? "needs no identities" : (spare_hit ? "spare" : "initialised"));
+  if (e == hipSuccess && (copy || init_table))
+    e = pgpu_launch_prologue(p, h_arena_dev, ws->arena.p, copy ? arena_bytes : 0, init_table, st);
+  if (e != hipSuccess) ws->arena_shadow.clear();
+  // ev0 .. ev1 spans this one kernel: its dispatch packet records both (no event packets around it)
+  static const bool ext_events = !env_flag("PGPU_FUSE_EVENT_PACKETS");
+  if (e == hipSuccess && !ext_events) e = hipEventRecord(ws->ev0, st);
+  if (e == hipSuccess)
+    e = ext_events ? pgpu_launch_query_direct(p, pl.grid, pl.dyn, st, ws->ev0, ws->ev1)
+                   : pgpu_launch_query_direct(p, pl.grid, pl.dyn, st);
+  if (e == hipSuccess && p.fuse_spare) {
+    Workspace::SpareSig& sg = tws->spare_sig;
+    sg.valid = true;
+    sg.G = p.G;
+    sg.nsec = p.nsec;
+    sg.mode = p.mode;
+    memcpy(sg.ops, p.sec_op, sizeof(int32_t) * p.nsec);
+  }
+  if (e == hipSuccess && !ext_events) e = hipEventRecord(ws->ev1, st);
+  *kernel_is_done = ext_events;  // (nothing is enqueued behind the kernel: no third packet either)
+  // completion of this query alone (later queries may already be queued behind it on the same stream)
+  if (e == hipSuccess && !ext_events) e = hipEventRecord(ws->done, st);
+  return launch_status(e);
+}
+
+int enqueue_compact(pgpu_context* ctx, Workspace* ws, const pgpu_table_layout* L, const void* dev_table,
+                    hipStream_t st, const pgpu_topk* order);
+
+// Three launches and whatever the query needs between them: prologue (arena copy, table identities), the kernels
+// that expand leaves, the query kernel(s), the filter statistic's kernels, finalize, and the eager compaction
+int enqueue_split(pgpu_context* ctx, const pgpu_table_layout& L, const Packer& pk, const LaunchPlan& pl,
+                  const ArenaLayout& A, const LeafWords& words, const TableTarget& t, const char* why, Workspace* ws,
+                  hipStream_t st, const DevParams& p) {
+  if (plan_trace_on()) fprintf(stderr, "[pgpu plan] launch split (%s): prologue, query kernels, finalize\n", why);
+  const char* d = (const char*)ws->arena.p;
+  const bool expand = any_leaf_expanded(pk);
+  void *h_arena_dev = nullptr, *h_stats_dev = nullptr;
+  hipError_t e = ws->h_arena.device_ptr(&h_arena_dev);
+  if (e == hipSuccess) e = ws->h_stats.device_ptr(&h_stats_dev);
+  ws->arena_shadow.clear();  // (the prologue below rewrites the arena; this path keeps no shadow)
+  if (e == hipSuccess) e = pgpu_launch_prologue(p, h_arena_dev, ws->arena.p, A.total, p.mode != PGPU_MODE_AGG, st);
+  if (e == hipSuccess) e = hipEventRecord(ws->ev0, st);
+  // raw-value leaves' match bitmaps (timed with the query: they are part of its filter)
+  if (e == hipSuccess && !pk.raws.empty())
+    e = pgpu_launch_rawpred((const RawLeaf*)(d + A.raw), (int)pk.raws.size(), words.raw, st);
+  if (e == hipSuccess && !pk.mvs.empty())
+    e = pgpu_launch_mvpred((const MvLeaf*)(d + A.mv), (int)pk.mvs.size(), words.mv, st);
+  if (e == hipSuccess && expand && p.direct != PGPU_KV_RKEY)
+    e = pgpu_launch_invexp((const InvLeafX*)(d + A.inv), (int)pk.invx.size(), words.inv, st);
+  if (e == hipSuccess && p.direct == PGPU_KV_RKEY) {
+    int64_t max_pairs = 0;
+    for (const InvLeafX& x : pk.invx) max_pairs = std::max<int64_t>(max_pairs, (int64_t)x.nids * x.nkeys);
+    e = pgpu_launch_rkey_ctab((const InvLeafX*)(d + A.inv), (int)pk.invx.size(), max_pairs,
+                              (DevContainer*)ws->rkctab.p, st);
+  }
+  if (e == hipSuccess && !pk.jobs.empty())
+    e = pgpu_launch_progbits(p, (const ProgJob*)(d + A.jobs), (int)pk.jobs.size(), pk.job_tiles, st);
+  if (e == hipSuccess)
+    e = p.pscan ? pgpu_launch_part_scan(p, pl.grid, pl.dyn, st)
+                : (p.direct != PGPU_KV_RING ? pgpu_launch_query_direct(p, pl.grid, pl.dyn, st)
+                                            : pgpu_launch_query(p, pl.grid, pl.dyn, st));
+  if (e == hipSuccess && p.mode == PGPU_MODE_PART) e = pgpu_launch_part_reduce(p, pl.grid, st);
+  // the reference's filter statistic (andfsm maps or leaf bitmaps for the host replay) is part of the query's
+  // kernels: ev0 .. ev1 spans every kernel that reads the segments, so kernel_ms prices the whole step's reads
+  if (e == hipSuccess && pk.fsm) {
+    void* h_ent_dev = nullptr;
+    e = ws->h_fsment.device_ptr(&h_ent_dev);
+    if (e == hipSuccess) e = pgpu_launch_andfsm(p, pk.fsm_s2, (uint32_t*)ws->fsmfn.p, (int64_t*)h_ent_dev, st);
+  }
+  if (e == hipSuccess && pk.leaf_words > 0) e = pgpu_launch_leafbits(p, st);
+  if (e == hipSuccess) e = hipEventRecord(ws->ev1, st);
+  // statistics, numSegmentsMatched flags and a small table into pinned host memory: one launch
+  if (e == hipSuccess) {
     void* h_seg_dev = nullptr;
-    if (e == hipSuccess) e = ws->h_segany.device_ptr(&h_seg_dev);
-    bool init_table = p.mode != PGPU_MODE_AGG, spare_hit = false;
-    if (e == hipSuccess && init_table) {
-      Workspace::SpareSig& sg = tws->spare_sig;
-      spare_hit = sg.valid && tws->spare.n >= need && sg.G == p.G && sg.nsec == p.nsec && sg.mode == p.mode &&
-                  memcmp(sg.ops, p.sec_op, sizeof(int32_t) * p.nsec) == 0;
-      if (spare_hit) {
-        std::swap(tws->table, tws->spare);
-        p.table = (int64_t*)tws->table.p;
-        init_table = false;
-      }
-      sg.valid = false;  // (until this query's kernel is enqueued: it writes the spare)
-      e = tws->spare.ensure(need, ctx->mpool, st);
-      p.fuse_spare = (int64_t*)tws->spare.p;
-    }
-    const bool copy = ws->arena_shadow.size() != total || memcmp(ws->arena_shadow.data(), h, total) != 0;
-    if (copy) ws->arena_shadow.assign(h, h + total);
-    p.fuse = 1;
-    p.fuse_nslabs = nwaves;
-    p.fuse_ticket = (uint32_t*)ws->ticket.p;
-    p.fuse_stats_out = (int64_t*)h_stats_dev;
-    p.fuse_seg_out = (uint8_t*)h_seg_dev;
-    p.fuse_host_table = host_table;
-    p.fuse_table_words = p.mode != PGPU_MODE_AGG ? table_words : 0;
-    if (trace)
-      fprintf(stderr, "[pgpu plan] launch fused: arena %s, table %s\n", copy ? "copied" : "resident",
-              p.mode == PGPU_MODE_AGG ? "needs no identities" : (spare_hit ? "spare" : "initialised"));
-    if (e == hipSuccess && (copy || init_table))
-      e = pgpu_launch_prologue(p, h_arena_dev, ws->arena.p, copy ? total : 0, init_table, st);
-    if (e != hipSuccess) ws->arena_shadow.clear();
-    // ev0 .. ev1 spans this one kernel: its dispatch packet records both (no event packets around it)
-    static const bool ext_events = !(getenv("PGPU_FUSE_EVENT_PACKETS") && atoi(getenv("PGPU_FUSE_EVENT_PACKETS")) != 0);
-    if (e == hipSuccess && !ext_events) e = hipEventRecord(ws->ev0, st);
+    e = ws->h_segany.device_ptr(&h_seg_dev);
     if (e == hipSuccess)
-      e = ext_events ? pgpu_launch_query_direct(p, grid, dyn, st, ws->ev0, ws->ev1)
-                     : pgpu_launch_query_direct(p, grid, dyn, st);
-    if (e == hipSuccess && p.fuse_spare) {
-      Workspace::SpareSig& sg = tws->spare_sig;
-      sg.valid = true;
-      sg.G = p.G;
-      sg.nsec = p.nsec;
-      sg.mode = p.mode;
-      memcpy(sg.ops, p.sec_op, sizeof(int32_t) * p.nsec);
+      e = pgpu_launch_finalize(p, pl.nwaves, (int64_t*)h_stats_dev, (uint8_t*)h_seg_dev, t.host_table,
+                               t.host_table ? pgpu_table_bytes(&L) / 8 : 0, st);
+  }
+  if (e == hipSuccess && p.mode == PGPU_MODE_HASH) {
+    // probe-overflow flag and the tracked segments' distinct-key counts, into pinned host memory
+    void* h_cnt_dev = nullptr;
+    if (p.segmask_rows) {
+      e = ws->h_segcnt.device_ptr(&h_cnt_dev);
+      if (e == hipSuccess) e = pgpu_launch_segcount(p, (int64_t*)h_cnt_dev, st);
     }
-    if (e == hipSuccess && !ext_events) e = hipEventRecord(ws->ev1, st);
-    kernel_is_done = ext_events;  // (nothing is enqueued behind the kernel: no third packet either)
-  } else {
-    if (trace) fprintf(stderr, "[pgpu plan] launch split (%s): prologue, query kernels, finalize\n", split_why);
-    ws->arena_shadow.clear();  // (the prologue below rewrites the arena; this path keeps no shadow)
-    if (e == hipSuccess) e = pgpu_launch_prologue(p, h_arena_dev, ws->arena.p, total, p.mode != PGPU_MODE_AGG, st);
-    if (e == hipSuccess) e = hipEventRecord(ws->ev0, st);
-    // raw-value leaves' match bitmaps (timed with the query: they are part of its filter)
-    if (e == hipSuccess && !pk.raws.empty())
-      e = pgpu_launch_rawpred((const RawLeaf*)(d + o_raw), (int)pk.raws.size(), max_raw_words, st);
-    if (e == hipSuccess && !pk.mvs.empty())
-      e = pgpu_launch_mvpred((const MvLeaf*)(d + o_mv), (int)pk.mvs.size(), max_mv_words, st);
-    if (e == hipSuccess && expand && p.direct != 5)
-      e = pgpu_launch_invexp((const InvLeafX*)(d + o_inv), (int)pk.invx.size(), max_inv_words, st);
-    if (e == hipSuccess && p.direct == 5) {
-      int64_t max_pairs = 0;
-      for (const InvLeafX& x : pk.invx) max_pairs = std::max<int64_t>(max_pairs, (int64_t)x.nids * x.nkeys);
-      e = pgpu_launch_rkey_ctab((const InvLeafX*)(d + o_inv), (int)pk.invx.size(), max_pairs,
-                                (DevContainer*)ws->rkctab.p, st);
-    }
-    if (e == hipSuccess && !pk.jobs.empty())
-      e = pgpu_launch_progbits(p, (const ProgJob*)(d + o_jobs), (int)pk.jobs.size(), pk.job_tiles, st);
-    if (e == hipSuccess)
-      e = p.pscan ? pgpu_launch_part_scan(p, grid, dyn, st)
-                  : (p.direct ? pgpu_launch_query_direct(p, grid, dyn, st) : pgpu_launch_query(p, grid, dyn, st));
-    if (e == hipSuccess && p.mode == PGPU_MODE_PART) e = pgpu_launch_part_reduce(p, grid, st);
-    // the reference's filter statistic (andfsm maps or leaf bitmaps for the host replay) is part of the query's
-    // kernels: ev0 .. ev1 spans every kernel that reads the segments, so kernel_ms prices the whole step's reads
-    if (e == hipSuccess && pk.fsm) {
-      void* h_ent_dev = nullptr;
-      e = ws->h_fsment.device_ptr(&h_ent_dev);
-      if (e == hipSuccess) e = pgpu_launch_andfsm(p, pk.fsm_s2, (uint32_t*)ws->fsmfn.p, (int64_t*)h_ent_dev, st);
-    }
-    if (e == hipSuccess && pk.leaf_words > 0) e = pgpu_launch_leafbits(p, st);
-    if (e == hipSuccess) e = hipEventRecord(ws->ev1, st);
-    // statistics, numSegmentsMatched flags and a small table into pinned host memory: one launch
-    if (e == hipSuccess) {
-      void* h_seg_dev = nullptr;
-      e = ws->h_segany.device_ptr(&h_seg_dev);
-      if (e == hipSuccess)
-        e = pgpu_launch_finalize(p, nwaves, (int64_t*)h_stats_dev, (uint8_t*)h_seg_dev, host_table,
-                                 host_table ? pgpu_table_bytes(&L) / 8 : 0, st);
-    }
-    if (e == hipSuccess && p.mode == PGPU_MODE_HASH) {
-      // probe-overflow flag and the tracked segments' distinct-key counts, into pinned host memory
-      void* h_cnt_dev = nullptr;
-      if (p.segmask_rows) {
-        e = ws->h_segcnt.device_ptr(&h_cnt_dev);
-        if (e == hipSuccess) e = pgpu_launch_segcount(p, (int64_t*)h_cnt_dev, st);
-      }
-      if (e == hipSuccess) e = hipMemcpyAsync((char*)ws->h_stats.p + 8 * PGPU_NSTATS, ws->hflag.p, 4, hipMemcpyDeviceToHost, st);
-    }
-    if (e == hipSuccess && pk.leaf_words > 0)
-      e = hipMemcpyAsync(ws->h_leafbits.p, ws->leafbits.p, 4ull * pk.leaf_words, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && eager) {
-      const int crc = enqueue_compact(ctx, ws, &L, dev_table, st, eager_order);
-      if (crc) return bail(crc);
-    }
+    if (e == hipSuccess) e = hipMemcpyAsync((char*)ws->h_stats.p + 8 * PGPU_NSTATS, ws->hflag.p, 4, hipMemcpyDeviceToHost, st);
+  }
+  if (e == hipSuccess && pk.leaf_words > 0)
+    e = hipMemcpyAsync(ws->h_leafbits.p, ws->leafbits.p, 4ull * pk.leaf_words, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && t.eager) {
+    const int crc = enqueue_compact(ctx, ws, &L, t.dev_table, st, t.eager_order);
+    if (crc) return crc;
   }
   // completion of this query alone (later queries may already be queued behind it on the same stream)
-  if (e == hipSuccess && !kernel_is_done) e = hipEventRecord(ws->done, st);
-  if (e != hipSuccess) return bail(fail(PGPU_E_HIP, "query launch: %s", hipGetErrorString(e)));
+  if (e == hipSuccess) e = hipEventRecord(ws->done, st);
+  return launch_status(e);
+}
 
-  host_timing().add(4, tl0, HostTiming::us());
+// The handle pgpu_query_wait reads: the launch's parameters, and what the host needs to finish the reference's
+// filter statistics (replay records, multi-value row offsets)
+pgpu_query* make_query_handle(pgpu_context* ctx, const pgpu_query_desc* q, const Packer& pk, const DevParams& p,
+                              int grid, Workspace* ws, hipStream_t st, hipEvent_t done, bool eager) {
   auto* qq = new pgpu_query();
   qq->ctx = ctx;
   qq->ws = ws;
-  qq->done = kernel_is_done ? ws->ev1 : ws->done;
+  qq->done = done;
   qq->eager = eager;
   qq->stream = st;
   qq->params = p;
@@ -3804,14 +3943,9 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
       const bool leaf = nd.op == PGPU_F_SCAN || nd.op == PGPU_F_INVERTED || nd.op == PGPU_F_SORTED ||
                         nd.op == PGPU_F_RAW_SCAN || nd.op == PGPU_F_RANGE_INDEX;
       if (!leaf) continue;
-      const HostColumn* hc = nullptr;
-      if (nd.op == PGPU_F_SCAN && nd.column >= 0 && nd.column < q->num_columns) {
-        const int32_t slot = sp.column_map[nd.column];
-        if (slot >= 0 && slot < (int32_t)sp.segment->cols.size()) hc = &sp.segment->cols[slot];
-      }
-      const bool mv = hc && hc->kind == PGPU_COL_MV;
-      leaf_off.push_back(mv ? hc->mv_offsets.data() : nullptr);
-      nmv += mv;
+      const HostColumn* mv = mv_scan_column(q, sp, nd);
+      leaf_off.push_back(mv ? mv->mv_offsets.data() : nullptr);
+      nmv += mv != nullptr;
     }
     if (nmv && sp.num_filter_nodes == 1) qq->mv_entries += sp.segment->cols[sp.column_map[sp.filter[0].column]].mv_values;
     else if (nmv) exact = false;
@@ -3833,11 +3967,87 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
   }
   qq->stats.filter_stats_exact = exact ? 1 : 0;
   qq->deadline_ms = q->deadline_ms;
+  return qq;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Every query enters the GPU here, as a sequence of phases: pack_query, drop_reference_replay and plan_launch (host
+// only), then ensure_workspace, fill_arena, enqueue_fused or enqueue_split, make_query_handle.
+// host_table (device-visible pointer into pinned host memory, or null): the finished table is also exported there
+// eager: compact the table (only the best groups by eager_order, when given) on the query's stream right behind
+// its kernels, into the workspace; pgpu_query_collect then only copies the rows out (pgpu_query_submit_ordered)
+// tws (pgpu_query_submit*): the workspace owning dev_table (its `table`); with it a register-direct query with a small
+// table runs as one launch (see Workspace::ticket) and may take the workspace's spare table as its table
+static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream, void* dev_table,
+                       uint64_t table_bytes, int64_t* host_table, pgpu_query** out_query, bool eager = false,
+                       const pgpu_topk* eager_order = nullptr, Workspace* tws = nullptr) {
+  if (!ctx || !q || !out_query) return fail(PGPU_E_INVALID, "null argument");
+  pgpu_table_layout L;
+  int rc = pgpu_table_layout_of(q, &L);
+  if (rc) return rc;
+  const uint64_t need = pgpu_table_bytes(&L);
+  if (!dev_table || table_bytes < need)
+    return fail(PGPU_E_INVALID, "table buffer %llu bytes < %llu needed", (unsigned long long)table_bytes,
+                (unsigned long long)need);
+  Packer pk;
+  DevParams p;
+  const double tp0 = HostTiming::us();
+  rc = pack_query(ctx, q, L, pk, p);
+  host_timing().add(2, tp0, HostTiming::us());
+  if (rc) return rc;
+  // host only: which kernel, grid and LDS size
+  drop_reference_replay(q, pk);
+  LaunchPlan pl;
+  rc = plan_launch(ctx->num_cus, q, L, pk, p, pl);
+  if (rc) return rc;
+
+  HIP_TRY(hipSetDevice(ctx->device));
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->lds_ready) {
+      HIP_TRY(pgpu_prepare_query_kernels(PGPU_LDS_LIMIT));
+      ctx->lds_ready = true;
+    }
+  }
+  const double tw0 = HostTiming::us();
+  Workspace* ws = acquire_ws(ctx, &rc);
+  if (!ws) return rc;
+  // from here every failure leaves through the one bail below
+  const TableTarget target{dev_table, host_table, eager, eager_order, tws};
+  const ArenaLayout A = arena_layout(pk);
+  hipStream_t st = nullptr;
+  bool expired = false, kernel_is_done = false;
+  rc = query_stream(ctx, stream, &st);
+  if (!rc) rc = ensure_workspace(ctx, q, L, pk, pl, A.total, ws, st, p);
+  if (!rc) {
+    const LeafWords words = fill_arena(pk, A, ws, dev_table, p);
+    const double tl0 = HostTiming::us();
+    host_timing().add(3, tw0, tl0);
+    // metadata in and stats (and small tables) out through pinned host memory touched by kernels: no DMA-engine
+    // copy sits between two queries' kernels
+    rc = launch_status(arm_cancel(q, ws, st, p, &expired));
+    const char* split_why = split_reason(q, L, pk, p, pl, target);
+    if (!rc)
+      rc = split_why ? enqueue_split(ctx, L, pk, pl, A, words, target, split_why, ws, st, p)
+                     : enqueue_fused(ctx, L, pl, A.total, target, ws, st, p, &kernel_is_done);
+    if (!rc) host_timing().add(4, tl0, HostTiming::us());
+  }
+  if (rc) {
+    // a bail after the query kernel was enqueued but before finalize_kernel: the matched-segment words it may
+    // have set must not count towards the workspace's next query (they are zero between queries)
+    if (st && ws->segany.p) (void)hipMemsetAsync(ws->segany.p, 0, ws->segany.n, st);
+    if (st && ws->ticket.p) (void)hipMemsetAsync(ws->ticket.p, 0, ws->ticket.n, st);
+    release_ws(ctx, ws);
+    return rc;
+  }
+  pgpu_query* qq = make_query_handle(ctx, q, pk, p, pl.grid, ws, st, kernel_is_done ? ws->ev1 : ws->done, eager);
   if (expired) qq->stop = PGPU_E_TIMEOUT;
   *out_query = qq;
   return PGPU_OK;
 }
-
 
 int pgpu_query_launch(pgpu_context* ctx, const pgpu_query_desc* q, void* stream, void* dev_table,
                       uint64_t table_bytes, pgpu_query** out_query) {
@@ -3984,13 +4194,13 @@ int pgpu_query_wait(pgpu_query* qq, pgpu_query_stats* out_stats) {
       }
   }
   if (qq->params.flags & PGPU_FLAG_PROFILE) {
-    const int nw = qq->grid * (qq->params.direct || qq->params.pscan ? 4 : PGPU_WAVES_OF(qq->params.dense));
+    const int nw = qq->grid * (qq->params.direct != PGPU_KV_RING || qq->params.pscan ? 4 : PGPU_WAVES_OF(qq->params.dense));
     std::vector<int64_t> pr((size_t)nw * PGPU_NPROF);
     HIP_TRY(hipMemcpy(pr.data(), qq->params.prof, pr.size() * 8, hipMemcpyDeviceToHost));
     double sum[PGPU_NPROF] = {0};
     int nl = 0, nc = 0;
     for (int w = 0; w < nw; ++w) {
-      const bool ld = !qq->params.direct && !qq->params.pscan &&
+      const bool ld = qq->params.direct == PGPU_KV_RING && !qq->params.pscan &&
                       (w % PGPU_WAVES_OF(qq->params.dense)) < PGPU_NLOAD_OF(qq->params.dense);
       ld ? ++nl : ++nc;
       for (int k = 0; k < PGPU_NPROF; ++k) sum[k] += (double)pr[(size_t)w * PGPU_NPROF + k];
