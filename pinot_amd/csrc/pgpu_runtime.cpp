@@ -324,6 +324,7 @@ struct Workspace {
     int32_t ops[PGPU_MAX_SECTIONS] = {};
   } spare_sig;
   bool busy = false;
+  uint64_t uses = 0;  // times acquire_ws handed it out (pgpu_context::Tail)
   ~Workspace() {
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
@@ -340,10 +341,38 @@ struct pgpu_context {
   std::mutex mu;
   std::vector<std::unique_ptr<Workspace>> pool;
   bool lds_ready = false;  // query kernels allowed the full 160 KiB of dynamic LDS
-  // pgpu_query_submit: all submitted queries run back to back on one stream (each kernel fills the GPU, so
-  // nothing is lost by serialising them, and their HIP events then time each kernel alone)
-  hipStream_t qstream = nullptr;
-  hipStream_t cstream = nullptr;  // pgpu_query_cancel: writes cancel words while the query stream is busy
+  // pgpu_query_submit: two query streams, created back to back (create_query_streams).  A query that runs as one
+  // launch (split_reason == nullptr, "fused") takes the stream the previous fused query did not use, so the
+  // workgroups of two neighbouring fused queries share the GPU while one drains and the other starts; never more
+  // than two, since a third kernel would only halve the rate of the second.  Every other query runs on qstream
+  // and shares the GPU with no other query of the context's streams: what is not ordered by the stream itself is
+  // ordered by one hipStreamWaitEvent on the earlier query's completion event (pick_stream).  Those queries see
+  // the GPU alone, so their HIP events time their kernels alone.  PGPU_QUERY_STREAMS=1: every query on qstream.
+  hipStream_t qstream = nullptr, qstream2 = nullptr;
+  int last_fused_stream = 1;  // (the first fused query runs on qstream)
+  // What pick_stream orders later queries behind: the last query placed on qstream2 and the last non-fused query
+  // (always on qstream), and whether the other stream already waited for it.  The event belongs to the query's
+  // workspace or ring slot; it still speaks of that query while the workspace was not taken again (`uses`), and
+  // once it was, the query has been released, hence finished, and needs no wait.
+  struct Tail {
+    hipEvent_t done = nullptr;
+    const Workspace* ws = nullptr;
+    uint64_t uses = 0;
+    bool other_is_behind = true;
+    bool live() const { return done && ws->uses == uses; }
+  } tail2, last_split;
+  // Kernel events (ev0, ev1) of fused queries, which outlive the query's workspace: the next fused query's
+  // kernel_ms starts at its predecessor's ev1 (pgpu_query_wait).  A ring keyed by the submit sequence number; a slot
+  // is claimed again only when its query was released, and a reader finds `seq` changed when it was.
+  struct EvSlot {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    uint64_t seq = 0;
+    bool held = false;
+  };
+  static constexpr int kEvRing = 64;
+  EvSlot evring[kEvRing];
+  uint64_t submit_seq = 0, last_fused_seq = 0;
+  hipStream_t cstream = nullptr;  // pgpu_query_cancel: writes cancel words while the query streams are busy
   // workspace buffers grow from this pool in stream order (DevMem::ensure(bytes, pool, stream)); it never returns
   // memory to the device on its own (release threshold = max), so no query-path allocation reaches the driver
   // twice.  nullptr when the device has no memory pools: growth then falls back to hipMalloc / hipFree.
@@ -357,7 +386,12 @@ struct pgpu_context {
   ~pgpu_context() {
     pool.clear();
     if (qstream) (void)hipStreamDestroy(qstream);
+    if (qstream2) (void)hipStreamDestroy(qstream2);
     if (cstream) (void)hipStreamDestroy(cstream);
+    for (EvSlot& s : evring) {
+      if (s.ev0) (void)hipEventDestroy(s.ev0);
+      if (s.ev1) (void)hipEventDestroy(s.ev1);
+    }
     if (mpool) {
       (void)hipDeviceSynchronize();
       (void)hipMemPoolDestroy(mpool);
@@ -456,6 +490,10 @@ struct pgpu_query {
   bool exact_filter = false;
   bool exact_fsm = false;  // the reference's count per segment from the andfsm kernels (pinned h_fsment)
   hipEvent_t done = nullptr;  // submitted queries: recorded after the last copy of this query
+  // the events around its kernels: the workspace's, or for a fused query of the context's streams those of ring
+  // slot `seq` (0: none); prev_seq: the fused query before it (0: none), whose ev1 bounds kernel_ms from below
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  uint64_t seq = 0, prev_seq = 0;
   // deadline (ms since the epoch, 0 = none) and why the query was stopped (0 = it was not)
   int64_t deadline_ms = 0;
   std::atomic<int> stop{0};  // PGPU_E_CANCELLED / PGPU_E_TIMEOUT
@@ -468,6 +506,7 @@ Workspace* acquire_ws(pgpu_context* ctx, int* err) {
   for (auto& w : ctx->pool)
     if (!w->busy) {
       w->busy = true;
+      ++w->uses;
       return w.get();
     }
   std::unique_ptr<Workspace> w(new Workspace());
@@ -481,6 +520,7 @@ Workspace* acquire_ws(pgpu_context* ctx, int* err) {
     return nullptr;
   }
   w->busy = true;
+  ++w->uses;
   ctx->pool.push_back(std::move(w));
   return ctx->pool.back().get();
 }
@@ -3477,10 +3517,19 @@ int plan_launch(int num_cus, const pgpu_query_desc* q, const pgpu_table_layout& 
 // The query's stream.  NULL: the context's query stream (queries run back to back; each has its own completion
 // event).  The cancel stream is created here too, never in pgpu_query_cancel (stream creation may wait for the
 // device).
+// (ctx->mu held.)  The two query streams are created back to back -- pgpu_query_submit calls this before it takes its
+// first workspace, so they are the context's first two streams -- which is what lets the runtime give them two
+// different hardware queues: kernels of two streams on one queue would run one after the other.
+hipError_t create_query_streams(pgpu_context* ctx) {
+  hipError_t e = ctx->qstream ? hipSuccess : hipStreamCreateWithFlags(&ctx->qstream, hipStreamNonBlocking);
+  if (e == hipSuccess && !ctx->qstream2) e = hipStreamCreateWithFlags(&ctx->qstream2, hipStreamNonBlocking);
+  return e;
+}
+
 int query_stream(pgpu_context* ctx, void* stream, hipStream_t* out) {
   std::lock_guard<std::mutex> lk(ctx->mu);
-  if (!stream && !ctx->qstream) {
-    const hipError_t ce = hipStreamCreateWithFlags(&ctx->qstream, hipStreamNonBlocking);
+  if (!stream) {
+    const hipError_t ce = create_query_streams(ctx);
     if (ce != hipSuccess) return fail(PGPU_E_HIP, "query stream: %s", hipGetErrorString(ce));
   }
   if (!ctx->cstream) {
@@ -3489,6 +3538,98 @@ int query_stream(pgpu_context* ctx, void* stream, hipStream_t* out) {
   }
   *out = stream ? (hipStream_t)stream : ctx->qstream;
   return PGPU_OK;
+}
+
+// Where a query runs and which events stand around its kernels
+struct StreamPick {
+  hipStream_t st = nullptr;
+  int index = -1;  // 0 / 1: the context's qstream / qstream2; -1: the caller's stream
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t done = nullptr;       // the query's completion event
+  uint64_t seq = 0, prev_seq = 0;  // ring slot of a fused query, and of the fused query before it (0: none)
+};
+
+// PGPU_FUSE_EVENT_PACKETS=1: a fused query's events are three event packets around its kernel; default: ev0 and ev1
+// ride on the kernel's dispatch packet and ev1 is also the completion event
+bool fuse_ext_events() {
+  static const bool ext = !env_flag("PGPU_FUSE_EVENT_PACKETS");
+  return ext;
+}
+
+// The stream of a query, once it is known whether it runs as one launch (fused).  On the context's own streams a
+// fused query takes the stream the previous fused query did not use and its kernel events from the ring; anything
+// else runs on qstream with its workspace's events.  Only two fused queries that are neighbours in submit order may
+// share the GPU.  A non-fused query shares it with nobody: qstream orders it behind whatever qstream holds and ahead
+// of whatever comes later on qstream; it waits for the last query on qstream2, and the first later query on qstream2
+// waits for it -- each a wait for that query's completion event, enqueued once (Tail::other_is_behind).  A run of
+// fused queries enqueues no wait.  (The order is about who shares the GPU with whom, not about data: queries in
+// flight share no buffer.)  Pick and bookkeeping are one critical section, so concurrent submits stay consistent;
+// which of them is "earlier" is then the order in which they get here.
+int pick_stream(pgpu_context* ctx, void* stream, bool fused, Workspace* ws, StreamPick* k) {
+  static const bool one_stream = env_int("PGPU_QUERY_STREAMS") == 1;
+  k->ev0 = ws->ev0;
+  k->ev1 = ws->ev1;
+  k->done = ws->done;
+  const int rc = query_stream(ctx, stream, &k->st);
+  if (rc || stream) return rc;
+  hipEvent_t wait_for = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    k->index = fused && !one_stream && ctx->last_fused_stream == 0 ? 1 : 0;
+    if (k->index) k->st = ctx->qstream2;
+    const uint64_t seq = ++ctx->submit_seq;
+    if (fused) {
+      ctx->last_fused_stream = k->index;
+      pgpu_context::EvSlot& s = ctx->evring[seq % pgpu_context::kEvRing];
+      // (a slot still held: more queries in flight than the ring is long -- this one keeps its workspace's events)
+      if (!s.held && !s.ev0 && hipEventCreate(&s.ev0) != hipSuccess) s.ev0 = nullptr;
+      if (!s.held && !s.ev1 && hipEventCreate(&s.ev1) != hipSuccess) s.ev1 = nullptr;
+      if (!s.held && s.ev0 && s.ev1) {
+        s.held = true;
+        s.seq = k->seq = seq;
+        k->ev0 = s.ev0;
+        k->ev1 = s.ev1;
+      }
+      k->prev_seq = ctx->last_fused_seq;
+      ctx->last_fused_seq = k->seq;
+      if (fuse_ext_events()) k->done = k->ev1;
+    }
+    pgpu_context::Tail* mine = !fused ? &ctx->last_split : (k->index ? &ctx->tail2 : nullptr);
+    pgpu_context::Tail* other = !fused ? &ctx->tail2 : (k->index ? &ctx->last_split : nullptr);
+    if (other && !other->other_is_behind) {
+      if (other->live()) wait_for = other->done;
+      other->other_is_behind = true;
+    }
+    if (mine) {
+      mine->done = k->done;
+      mine->ws = ws;
+      mine->uses = ws->uses;
+      mine->other_is_behind = false;
+    }
+  }
+  if (plan_trace_on()) {
+    fprintf(stderr, "[pgpu plan] stream %d of %d\n", k->index, one_stream ? 1 : 2);
+    if (wait_for) fprintf(stderr, "[pgpu plan] order: waits for the last query on stream %d\n", 1 - k->index);
+  }
+  if (wait_for) {
+    const hipError_t e = hipStreamWaitEvent(k->st, wait_for, 0);
+    if (e != hipSuccess) return fail(PGPU_E_HIP, "query order: %s", hipGetErrorString(e));
+  }
+  return PGPU_OK;
+}
+
+// The query's ring slot may be claimed again (its events stay readable until it is).  failed: the query was never
+// enqueued, so nobody may read its events, and the next fused query's predecessor is again the one before it.
+void release_ev_slot(pgpu_context* ctx, const StreamPick& k, bool failed = false) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (k.seq) {
+    pgpu_context::EvSlot& s = ctx->evring[k.seq % pgpu_context::kEvRing];
+    if (s.seq == k.seq) {
+      s.held = false;
+      if (failed) s.seq = 0;
+    }
+  }
+  if (failed && k.index >= 0 && ctx->last_fused_seq == k.seq) ctx->last_fused_seq = k.prev_seq;
 }
 
 // The metadata arena: one host image of 13 sections (each 16-byte aligned) that the prologue copies to the device
@@ -3773,7 +3914,8 @@ int launch_status(hipError_t e) {
 // workspace's spare table when the previous fused query prepared it for this layout.  *kernel_is_done: the query
 // kernel's own end event (ev1) also says the query is complete.
 int enqueue_fused(pgpu_context* ctx, const pgpu_table_layout& L, const LaunchPlan& pl, size_t arena_bytes,
-                  const TableTarget& t, Workspace* ws, hipStream_t st, DevParams& p, bool* kernel_is_done) {
+                  const TableTarget& t, Workspace* ws, const StreamPick& k, DevParams& p, bool* kernel_is_done) {
+  const hipStream_t st = k.st;
   Workspace* tws = t.tws;
   const uint64_t need = pgpu_table_bytes(&L);
   void *h_arena_dev = nullptr, *h_stats_dev = nullptr, *h_seg_dev = nullptr;
@@ -3790,6 +3932,8 @@ int enqueue_fused(pgpu_context* ctx, const pgpu_table_layout& L, const LaunchPla
     spare_hit = sg.valid && tws->spare.n >= need && sg.G == p.G && sg.nsec == p.nsec && sg.mode == p.mode &&
                 memcmp(sg.ops, p.sec_op, sizeof(int32_t) * p.nsec) == 0;
     if (spare_hit) {
+      // (the query that filled the spare may have run on the other query stream: no wait is needed, since a
+      // workspace is taken again only after its query was collected, hence finished)
       std::swap(tws->table, tws->spare);
       p.table = (int64_t*)tws->table.p;
       init_table = false;
@@ -3815,10 +3959,10 @@ int enqueue_fused(pgpu_context* ctx, const pgpu_table_layout& L, const LaunchPla
     e = pgpu_launch_prologue(p, h_arena_dev, ws->arena.p, copy ? arena_bytes : 0, init_table, st);
   if (e != hipSuccess) ws->arena_shadow.clear();
   // ev0 .. ev1 spans this one kernel: its dispatch packet records both (no event packets around it)
-  static const bool ext_events = !env_flag("PGPU_FUSE_EVENT_PACKETS");
-  if (e == hipSuccess && !ext_events) e = hipEventRecord(ws->ev0, st);
+  const bool ext_events = fuse_ext_events();
+  if (e == hipSuccess && !ext_events) e = hipEventRecord(k.ev0, st);
   if (e == hipSuccess)
-    e = ext_events ? pgpu_launch_query_direct(p, pl.grid, pl.dyn, st, ws->ev0, ws->ev1)
+    e = ext_events ? pgpu_launch_query_direct(p, pl.grid, pl.dyn, st, k.ev0, k.ev1)
                    : pgpu_launch_query_direct(p, pl.grid, pl.dyn, st);
   if (e == hipSuccess && p.fuse_spare) {
     Workspace::SpareSig& sg = tws->spare_sig;
@@ -3828,7 +3972,7 @@ int enqueue_fused(pgpu_context* ctx, const pgpu_table_layout& L, const LaunchPla
     sg.mode = p.mode;
     memcpy(sg.ops, p.sec_op, sizeof(int32_t) * p.nsec);
   }
-  if (e == hipSuccess && !ext_events) e = hipEventRecord(ws->ev1, st);
+  if (e == hipSuccess && !ext_events) e = hipEventRecord(k.ev1, st);
   *kernel_is_done = ext_events;  // (nothing is enqueued behind the kernel: no third packet either)
   // completion of this query alone (later queries may already be queued behind it on the same stream)
   if (e == hipSuccess && !ext_events) e = hipEventRecord(ws->done, st);
@@ -3974,13 +4118,15 @@ pgpu_query* make_query_handle(pgpu_context* ctx, const pgpu_query_desc* q, const
 
 extern "C" {
 
-// Every query enters the GPU here, as a sequence of phases: pack_query, drop_reference_replay and plan_launch (host
-// only), then ensure_workspace, fill_arena, enqueue_fused or enqueue_split, make_query_handle.
+// Every query enters the GPU here, as a sequence of phases: pack_query, drop_reference_replay, plan_launch and
+// split_reason (host only), then pick_stream, ensure_workspace, fill_arena, enqueue_fused or enqueue_split,
+// make_query_handle.
 // host_table (device-visible pointer into pinned host memory, or null): the finished table is also exported there
 // eager: compact the table (only the best groups by eager_order, when given) on the query's stream right behind
 // its kernels, into the workspace; pgpu_query_collect then only copies the rows out (pgpu_query_submit_ordered)
-// tws (pgpu_query_submit*): the workspace owning dev_table (its `table`); with it a register-direct query with a small
-// table runs as one launch (see Workspace::ticket) and may take the workspace's spare table as its table
+// tws (pgpu_query_submit*): the workspace whose `table` is the query's table (dev_table is not read: the table is
+// grown here, on the query's stream); with it a register-direct query with a small table runs as one launch (see
+// Workspace::ticket) and may take the workspace's spare table as its table
 static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream, void* dev_table,
                        uint64_t table_bytes, int64_t* host_table, pgpu_query** out_query, bool eager = false,
                        const pgpu_topk* eager_order = nullptr, Workspace* tws = nullptr) {
@@ -3989,7 +4135,8 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
   int rc = pgpu_table_layout_of(q, &L);
   if (rc) return rc;
   const uint64_t need = pgpu_table_bytes(&L);
-  if (!dev_table || table_bytes < need)
+  // (tws: the table is tws->table, grown below on the stream the query runs on)
+  if (!tws && (!dev_table || table_bytes < need))
     return fail(PGPU_E_INVALID, "table buffer %llu bytes < %llu needed", (unsigned long long)table_bytes,
                 (unsigned long long)need);
   Packer pk;
@@ -3998,11 +4145,13 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
   rc = pack_query(ctx, q, L, pk, p);
   host_timing().add(2, tp0, HostTiming::us());
   if (rc) return rc;
-  // host only: which kernel, grid and LDS size
+  // host only: which kernel, grid and LDS size, and with them whether the query is one launch or three
   drop_reference_replay(q, pk);
   LaunchPlan pl;
   rc = plan_launch(ctx->num_cus, q, L, pk, p, pl);
   if (rc) return rc;
+  TableTarget target{dev_table, host_table, eager, eager_order, tws};
+  const char* split_why = split_reason(q, L, pk, p, pl, target);
 
   HIP_TRY(hipSetDevice(ctx->device));
   {
@@ -4016,11 +4165,16 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
   Workspace* ws = acquire_ws(ctx, &rc);
   if (!ws) return rc;
   // from here every failure leaves through the one bail below
-  const TableTarget target{dev_table, host_table, eager, eager_order, tws};
   const ArenaLayout A = arena_layout(pk);
-  hipStream_t st = nullptr;
+  StreamPick pick;
   bool expired = false, kernel_is_done = false;
-  rc = query_stream(ctx, stream, &st);
+  rc = pick_stream(ctx, stream, !split_why, ws, &pick);
+  const hipStream_t st = pick.st;
+  if (!rc && tws) {
+    const hipError_t te = tws->table.ensure(need, ctx->mpool, st);
+    if (te != hipSuccess) rc = fail(PGPU_E_HIP, "table allocation: %s", hipGetErrorString(te));
+    target.dev_table = dev_table = tws->table.p;
+  }
   if (!rc) rc = ensure_workspace(ctx, q, L, pk, pl, A.total, ws, st, p);
   if (!rc) {
     const LeafWords words = fill_arena(pk, A, ws, dev_table, p);
@@ -4029,10 +4183,9 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
     // metadata in and stats (and small tables) out through pinned host memory touched by kernels: no DMA-engine
     // copy sits between two queries' kernels
     rc = launch_status(arm_cancel(q, ws, st, p, &expired));
-    const char* split_why = split_reason(q, L, pk, p, pl, target);
     if (!rc)
       rc = split_why ? enqueue_split(ctx, L, pk, pl, A, words, target, split_why, ws, st, p)
-                     : enqueue_fused(ctx, L, pl, A.total, target, ws, st, p, &kernel_is_done);
+                     : enqueue_fused(ctx, L, pl, A.total, target, ws, pick, p, &kernel_is_done);
     if (!rc) host_timing().add(4, tl0, HostTiming::us());
   }
   if (rc) {
@@ -4040,10 +4193,18 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
     // have set must not count towards the workspace's next query (they are zero between queries)
     if (st && ws->segany.p) (void)hipMemsetAsync(ws->segany.p, 0, ws->segany.n, st);
     if (st && ws->ticket.p) (void)hipMemsetAsync(ws->ticket.p, 0, ws->ticket.n, st);
+    // (the workspace's next query may run on the other query stream: what was enqueued here ends first)
+    if (st && pick.index >= 0) (void)hipStreamSynchronize(st);
+    release_ev_slot(ctx, pick, true);
     release_ws(ctx, ws);
     return rc;
   }
-  pgpu_query* qq = make_query_handle(ctx, q, pk, p, pl.grid, ws, st, kernel_is_done ? ws->ev1 : ws->done, eager);
+  const hipEvent_t done = kernel_is_done ? pick.ev1 : ws->done;  // (= pick.done)
+  pgpu_query* qq = make_query_handle(ctx, q, pk, p, pl.grid, ws, st, done, eager);
+  qq->ev0 = pick.ev0;
+  qq->ev1 = pick.ev1;
+  qq->seq = pick.seq;
+  qq->prev_seq = pick.prev_seq;
   if (expired) qq->stop = PGPU_E_TIMEOUT;
   *out_query = qq;
   return PGPU_OK;
@@ -4124,7 +4285,18 @@ int pgpu_query_wait(pgpu_query* qq, pgpu_query_stats* out_stats) {
     if (qq->matched_out) memcpy(qq->matched_out, f, (size_t)qq->params.nseg);
   }
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, qq->ws->ev0, qq->ws->ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, qq->ev0, qq->ev1));
+  if (qq->prev_seq) {
+    // a fused query may share the GPU with the fused query before it: its time starts where that one's kernel
+    // ended, if that is later than its own start.  (The predecessor's events are gone once its ring slot was
+    // claimed again; they are not ready when this query is collected before it: then the own start stands.)
+    std::lock_guard<std::mutex> lk(qq->ctx->mu);
+    const pgpu_context::EvSlot& s = qq->ctx->evring[qq->prev_seq % pgpu_context::kEvRing];
+    float since = 0.f;
+    if (s.seq == qq->prev_seq && hipEventQuery(s.ev1) == hipSuccess &&
+        hipEventElapsedTime(&since, s.ev1, qq->ev1) == hipSuccess)
+      ms = std::max(0.f, std::min(ms, since));
+  }
   qq->stats.kernel_ms = ms;
   qq->stats.kernel_variant = qq->params.pscan ? PGPU_KV_PSCAN : qq->params.direct;
   if (const int st = qq->stop.load()) {
@@ -4223,6 +4395,11 @@ int pgpu_query_release(pgpu_query* qq) {
   else (void)hipStreamSynchronize(qq->stream);
   if (qq->tws) release_ws(qq->ctx, qq->tws);
   release_ws(qq->ctx, qq->ws);
+  if (qq->seq) {
+    StreamPick k;
+    k.seq = qq->seq;
+    release_ev_slot(qq->ctx, k);
+  }
   delete qq;
   return PGPU_OK;
 }
@@ -4875,17 +5052,13 @@ static int submit_impl(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_t
   HIP_TRY(hipSetDevice(ctx->device));
   {
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (!ctx->qstream) HIP_TRY(hipStreamCreateWithFlags(&ctx->qstream, hipStreamNonBlocking));
+    HIP_TRY(create_query_streams(ctx));  // before the first workspace's stream
   }
   int err = 0;
-  Workspace* tws = acquire_ws(ctx, &err);  // owns the partial table until pgpu_query_collect
+  // owns the partial table until pgpu_query_collect (launch_impl grows it, on the stream it picks for the query)
+  Workspace* tws = acquire_ws(ctx, &err);
   if (!tws) return err;
   const uint64_t bytes = pgpu_table_bytes(&L);
-  hipError_t e = tws->table.ensure(bytes, ctx->mpool, ctx->qstream);
-  if (e != hipSuccess) {
-    release_ws(ctx, tws);
-    return fail(PGPU_E_HIP, "table allocation: %s", hipGetErrorString(e));
-  }
   // small tables (aggregation only, or up to a few hundred thousand keys) are exported whole into pinned host
   // memory right behind the kernel and compacted on the host: pgpu_query_collect then synchronises once
   // (PGPU_Q_FOLD: the table is folded on the device at collect; neither exported nor compacted as it stands)
@@ -4893,7 +5066,7 @@ static int submit_impl(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_t
   const bool small = !folded && bytes <= (8u << 20);
   void* h_table_dev = nullptr;
   if (small) {
-    e = tws->h_table.ensure(bytes);
+    hipError_t e = tws->h_table.ensure(bytes);
     if (e == hipSuccess) e = tws->h_table.device_ptr(&h_table_dev);
     if (e != hipSuccess) {
       release_ws(ctx, tws);
@@ -4905,7 +5078,7 @@ static int submit_impl(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_t
   // wait in collect() behind query i+1's kernel, which holds every CU (the table stays intact, so a collect with
   // another order still selects from it)
   const bool ordered = order && order->k > 0 && L.num_keys > order->k;
-  rc = launch_impl(ctx, q, ctx->qstream, tws->table.p, tws->table.n, (int64_t*)h_table_dev, &qq, !small && !folded,
+  rc = launch_impl(ctx, q, nullptr, nullptr, 0, (int64_t*)h_table_dev, &qq, !small && !folded,
                    ordered ? order : nullptr, tws);
   if (rc) {
     release_ws(ctx, tws);
