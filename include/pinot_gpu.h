@@ -697,6 +697,42 @@ int pgpu_query_execute(pgpu_context* ctx, const pgpu_query_desc* q, int64_t* out
 int pgpu_filter_entries_scanned(const pgpu_filter_node* nodes, int32_t num_nodes, const uint32_t* const* leaf_bits,
                                 int32_t num_leaves, int32_t num_docs, int64_t* out);
 
+/* ---- register-direct lead leaf: the planner's byte model (host only, no device needed) ---------------------
+ * A top-level AND streams its first child A's bit planes and gathers the later children per candidate doc.  When a
+ * later child B -- one non-negated RANGE / IN scan leaf on a bit-sliced fixed-bit column -- is far more selective,
+ * the planner streams only the top P planes of B's column instead: the docs whose top P id bits can match gather
+ * B's exact id, and only B's matches gather A.  Modelled DRAM bytes per 2048-doc tile (a gather moves one 128-B
+ * line):
+ *   today   = 256 bits_a + (prefix pre-filter ? 256 * 3 + cand * covered * 128 : cand * 128),  cand = rho_dense * 2048
+ *   lead(P) = 256 P + 2048 * cov_P * 128 + 2048 * sel_b * 128 * num_dense_scans
+ * P is one of the kernel's widths 8 / 10 / 12 / 16 below bits_b, or bits_b itself when bits_b <= 16 (the lead leaf is
+ * then exact, B is not gathered again and the middle term is absent); a width whose matching prefixes do not merge
+ * into at most 4 ranges is not admissible.  pgpu_lead_model returns the admissible P with the lowest lead(P)
+ * (planes == 0: none).
+ *   bits_a           planes today's plan streams for the filter (its dense children's columns)
+ *   rho_dense        share of the docs today's dense children keep
+ *   residual_kind    today's residual program: none, B alone (the prefix pre-filter's shape), anything else
+ *   num_dense_scans  today's dense children other than B (each is gathered for B's matches under the lead plan)
+ *   bits_b, sel_b    B's column width and the share of docs B keeps
+ *   runs             B's matching dict ids as num_runs pairs [lo, hi)
+ * A query switches when its segments' tiles together save at least the threshold (pgpu_lead_switch):
+ * pgpu_lead_switch_bytes() is 32 MiB -- about one launch boundary at the HBM stream rate -- unless
+ * PGPU_LEAD_SWITCH_BYTES overrides it (0: whenever cheaper, negative: never). */
+#define PGPU_LEAD_RESID_NONE 0
+#define PGPU_LEAD_RESID_B 1
+#define PGPU_LEAD_RESID_OTHER 2
+typedef struct pgpu_lead_model_out {
+  int32_t planes;         /* P; 0 = no admissible width */
+  int32_t num_ranges;     /* ranges [lo, hi) of the top P id bits that can match */
+  uint32_t ranges[4][2];
+  double today_bytes;     /* per tile, the plan in query order */
+  double lead_bytes;      /* per tile, led by B's top P planes */
+} pgpu_lead_model_out;
+int pgpu_lead_model(int32_t bits_a, double rho_dense, int32_t residual_kind, int32_t num_dense_scans, int32_t bits_b,
+                    double sel_b, const uint32_t* runs, int32_t num_runs, pgpu_lead_model_out* out);
+int64_t pgpu_lead_switch_bytes(void);
+int32_t pgpu_lead_switch(double saved_bytes, int64_t threshold_bytes);
+
 /* MIN/MAX order-preserving key -> double (value_type = stored type of the aggregated column). */
 double pgpu_decode_minmax_key(int64_t key, int32_t value_type);
 

@@ -155,6 +155,25 @@ class ExprNode(C.Structure):
                 ("values", C.POINTER(Literal))]
 
 
+PGPU_LEAD_RESID_NONE, PGPU_LEAD_RESID_B, PGPU_LEAD_RESID_OTHER = range(3)
+
+
+class LeadModelOut(C.Structure):
+    _fields_ = [("planes", C.c_int32), ("num_ranges", C.c_int32), ("ranges", (C.c_uint32 * 2) * 4),
+                ("today_bytes", C.c_double), ("lead_bytes", C.c_double)]
+
+
+def lead_model(bits_a: int, rho_dense: float, residual_kind: int, num_dense_scans: int, bits_b: int, sel_b: float,
+               runs) -> LeadModelOut:
+    """pgpu_lead_model: the planner's byte model of leading with the top planes of a later AND child (host only).
+    runs: the child's matching dict ids as (lo, hi) pairs, hi exclusive."""
+    flat = (C.c_uint32 * max(1, 2 * len(runs)))(*[int(x) for r in runs for x in r])
+    out = LeadModelOut()
+    check(load().pgpu_lead_model(bits_a, rho_dense, residual_kind, num_dense_scans, bits_b, sel_b, flat, len(runs),
+                                 C.byref(out)))
+    return out
+
+
 # exported symbols and their signatures: (name, restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = [
@@ -235,6 +254,10 @@ SIGNATURES = [
     ("pgpu_filter_entries_scanned", C.c_int, [C.POINTER(FilterNode), C.c_int32, C.POINTER(C.POINTER(C.c_uint32)),
                                              C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     ("pgpu_kernel_geometry", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("pgpu_lead_model", C.c_int, [C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                  C.POINTER(C.c_uint32), C.c_int32, C.POINTER(LeadModelOut)]),
+    ("pgpu_lead_switch_bytes", C.c_int64, []),
+    ("pgpu_lead_switch", C.c_int32, [C.c_double, C.c_int64]),
 ]
 
 _lib = None

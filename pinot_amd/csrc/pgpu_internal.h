@@ -147,7 +147,10 @@ struct DevSeg {
   // BITS leaves of the dense program (their instructions' n = slot): the query kernel loads their words for a
   // tile together before interpreting the program, one round trip instead of one per leaf
   int32_t nbits;
-  int32_t pad2_;
+  // register-direct lead leaf (lead_choice in pgpu_runtime.cpp): the fast leaf is the top bits - f_plane0 planes of
+  // its column -- plane k of the leaf is plane f_plane0 + k of the tile -- and f_rng holds ranges of those top bits
+  // (0: the whole column, ranges of dict ids)
+  int32_t f_plane0;
   const uint32_t* bits_w[PGPU_PREBITS];
   // register-direct prefix pre-filter (DevParams::rd_pfx planes): the residual SCAN leaf's query column (-1: none)
   // and the ranges [lo, hi) of its ids' top rd_pfx bits that can match, OR-ed -- a candidate outside them cannot

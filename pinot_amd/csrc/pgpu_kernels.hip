@@ -2783,6 +2783,7 @@ FI void fused_finalize(const DevParams& p, unsigned char* smem) {
 struct RdIssue {  // the issue cursor's segment: its sliced column (and the prefix column's)
   const uint32_t* sliced;
   int bits;
+  int plane0;  // DevSeg::f_plane0: the leaf is the column's planes [plane0, bits)
   const uint32_t* psliced;
   int pbits;
 };
@@ -2792,16 +2793,18 @@ FI void rd_load_issue(const DevParams& p, int seg, RdIssue& is) {
   const int qc = cld(&sg->stage_col[0]);
   is.sliced = (const uint32_t*)cld(&cols[qc].sliced);
   is.bits = cld(&cols[qc].bits);
+  is.plane0 = cld(&sg->f_plane0);
   const int pc = cld(&sg->pfx_col);
   is.psliced = pc >= 0 ? (const uint32_t*)cld(&cols[pc].sliced) : nullptr;
   is.pbits = pc >= 0 ? cld(&cols[pc].bits) : 0;
 }
 template <int PL>
 FI void rd_load_tile(const RdIssue& is, int tile_in_seg, uint32_t (&x)[PL]) {
-  const uint32_t* src = is.sliced + (size_t)tile_in_seg * is.bits * 64 + lane_id();
+  const uint32_t* src = is.sliced + ((size_t)tile_in_seg * is.bits + is.plane0) * 64 + lane_id();
+  const int np = is.bits - is.plane0;
 #pragma unroll
   for (int k = 0; k < PL; ++k)
-    x[k] = k < is.bits ? __builtin_nontemporal_load(src + 64 * k) : 0u;  // planes past the width: 0 (inert below)
+    x[k] = k < np ? __builtin_nontemporal_load(src + 64 * k) : 0u;  // planes past the width: 0 (inert below)
 }
 // The residual column's top PK planes (plane j of the prefix = bit pbits - PK + j of the id)
 template <int PK>
@@ -2921,7 +2924,8 @@ FI Stats rdirect_consumer(const DevParams& p, const Lds& L, int cidx, int t0, in
           const int ndocs = min(WT, ss.num_docs - doc0);
           const int rem = ndocs - 32 * lane;
           valid = rem >= 32 ? 0xFFFFFFFFu : (rem <= 0 ? 0u : ((1u << rem) - 1u));
-          if ((p.flags & PGPU_FLAG_STATS) && lane == 0) dense_bytes += ((int64_t)ndocs * (ss.f_bits[0] + PK) + 7) / 8;
+          if ((p.flags & PGPU_FLAG_STATS) && lane == 0)
+            dense_bytes += ((int64_t)ndocs * (ss.f_bits[0] - cld(&ss.sg->f_plane0) + PK) + 7) / 8;
         }
         uint32_t mm = rd_filter(ss, x[s], valid, lane_scanned);
         if constexpr (PK > 0) mm = rd_prefix<PK>(ss, y[s], mm, lane_scanned);

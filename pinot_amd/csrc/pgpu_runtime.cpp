@@ -2230,6 +2230,80 @@ double line_touch(double rho, int bits) {
 }
 constexpr int kMaxSlotBytes = 27 * 1024;  // keeps >= 3 ring slots next to the consumer areas
 
+// The ranges [lo, hi) of the top K bits of a `bits`-wide column's ids that the id runs [a, b) reach, merged, and the
+// share of the 2^K prefixes they cover.  False when there is none or more than PGPU_SLICE_RANGES.
+bool prefix_ranges(const std::vector<std::pair<uint64_t, uint64_t>>& runs, int bits, int K,
+                   std::vector<std::pair<uint32_t, uint32_t>>& merged, double* covered) {
+  const int sh = bits - K;
+  std::vector<std::pair<uint32_t, uint32_t>> pr;
+  for (auto& r : runs) pr.emplace_back((uint32_t)(r.first >> sh), (uint32_t)(((r.second - 1) >> sh) + 1));
+  std::sort(pr.begin(), pr.end());
+  merged.clear();
+  for (auto& r : pr) {
+    if (!merged.empty() && r.first <= merged.back().second) merged.back().second = std::max(merged.back().second, r.second);
+    else merged.push_back(r);
+  }
+  if (merged.empty() || (int)merged.size() > PGPU_SLICE_RANGES) return false;
+  *covered = 0;
+  for (auto& r : merged) *covered += r.second - r.first;
+  *covered /= (double)(1ull << K);
+  return true;
+}
+
+// Lead leaf of the register-direct kernel (pgpu_lead_model in pinot_gpu.h; plan_segment plans with this function).
+// A top-level AND streams its first child A and gathers the later ones per candidate.  When a later child B is far
+// more selective than A, streaming only the top P planes of B's column rejects 1 - 2^-P of the docs before anything
+// else is read: the survivors gather B's exact id (one 128-B line each, tools/gather_policy_bench.hip), and only
+// B's matches gather A.  Bytes per 2048-doc tile:
+//   today   = 256 bits_A + (prefix pre-filter ? 256 PGPU_PFX_PLANES + cand covered 128 : cand 128)
+//   lead(P) = 256 P + 2048 cov_P 128 + 2048 sel_B 128 (former dense scan children)
+// with cand = rho_dense 2048 candidates per tile; P = bits_B makes the lead leaf exact, B is not gathered again and
+// the middle term is absent.  P is one of query_kernel_rdirect's widths below bits_B, or bits_B itself up to 16.
+constexpr int kLeadWidths[4] = {8, 10, 12, 16};
+// A query switches when its segments together save at least this much: ~5 us at the 6.3 TB/s stream rate, one launch
+// boundary -- below it nothing can be observed, and small queries keep their plan.  PGPU_LEAD_SWITCH_BYTES overrides
+// (0: whenever cheaper, -1: never; read per plan: tests).
+constexpr int64_t kLeadSwitchBytes = 32ll << 20;
+// plan_segment / pack_query: the lead leaf did not pack as one staged SCAN -- not an error, pack_and_plan packs the
+// query again in query order (no PGPU_E_* code: those are negative)
+constexpr int kLeadRetry = 1;
+void lead_model(int bits_a, double rho_dense, int residual_kind, int num_dense_scans, int bits_b, double sel_b,
+                const std::vector<std::pair<uint64_t, uint64_t>>& runs, pgpu_lead_model_out* out) {
+  memset(out, 0, sizeof(*out));
+  const double cand = rho_dense * PGPU_WT;
+  out->today_bytes = 256.0 * bits_a;
+  if (residual_kind == PGPU_LEAD_RESID_B) {  // plan_prefix's rule
+    const int K = PGPU_PFX_PLANES;
+    std::vector<std::pair<uint32_t, uint32_t>> m;
+    double cov = 1.0;
+    if (bits_b > K && prefix_ranges(runs, bits_b, K, m, &cov) && cand * 128.0 * (1.0 - cov) > 256.0 * K)
+      out->today_bytes += 256.0 * K + cand * cov * 128.0;
+    else
+      out->today_bytes += cand * 128.0;
+  } else if (residual_kind == PGPU_LEAD_RESID_OTHER) {
+    out->today_bytes += cand * 128.0;
+  }
+  auto consider = [&](int P) {
+    std::vector<std::pair<uint32_t, uint32_t>> m;
+    double cov;
+    if (!prefix_ranges(runs, bits_b, P, m, &cov)) return;
+    const double lead = 256.0 * P + (P < bits_b ? PGPU_WT * cov * 128.0 : 0.0) +
+                        PGPU_WT * sel_b * 128.0 * num_dense_scans;
+    // (a tie goes to the exact leaf, which gathers less than the model's line per survivor)
+    if (out->planes && (P < bits_b ? lead >= out->lead_bytes : lead > out->lead_bytes)) return;
+    out->planes = P;
+    out->lead_bytes = lead;
+    out->num_ranges = (int32_t)m.size();
+    for (int r = 0; r < PGPU_SLICE_RANGES; ++r) {
+      out->ranges[r][0] = r < (int)m.size() ? m[r].first : 0;
+      out->ranges[r][1] = r < (int)m.size() ? m[r].second : 0;
+    }
+  };
+  for (int P : kLeadWidths)
+    if (P < bits_b) consider(P);
+  if (bits_b <= 16) consider(bits_b);
+}
+
 // Prefix pre-filter for the register-direct kernel (DevSeg::pfx_*): when the residual program is one SCAN leaf on a
 // fixed-bit column with a bit-sliced copy, the top PGPU_PFX_PLANES planes of that column can be streamed beside the
 // fast leaf, and a candidate whose id's top bits fall outside every matching id run is rejected without its
@@ -2261,19 +2335,9 @@ void plan_prefix(const SegView& v, const Packer& pk, double rho_dense, DevSeg& d
   } else {
     return;
   }
-  const int sh = dc->bits - K;
-  std::vector<std::pair<uint32_t, uint32_t>> pr;  // prefix ranges, merged
-  for (auto& r : runs) pr.emplace_back((uint32_t)(r.first >> sh), (uint32_t)(((r.second - 1) >> sh) + 1));
-  std::sort(pr.begin(), pr.end());
   std::vector<std::pair<uint32_t, uint32_t>> merged;
-  for (auto& r : pr) {
-    if (!merged.empty() && r.first <= merged.back().second) merged.back().second = std::max(merged.back().second, r.second);
-    else merged.push_back(r);
-  }
-  if (merged.empty() || (int)merged.size() > PGPU_SLICE_RANGES) return;
-  double covered = 0;
-  for (auto& r : merged) covered += r.second - r.first;
-  covered /= (double)(1u << K);
+  double covered;
+  if (!prefix_ranges(runs, dc->bits, K, merged, &covered)) return;
   const double cand = rho_dense * PGPU_WT;  // candidates per 2048-doc tile
   if (cand * 128.0 * (1.0 - covered) <= 256.0 * K) return;
   ds.pfx_col = in.col;
@@ -2284,16 +2348,22 @@ void plan_prefix(const SegView& v, const Packer& pk, double rho_dense, DevSeg& d
   }
 }
 
-int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pgpu_segment* seg,
-                 const DevParams& p, Packer& pk, DevSeg& ds) {
-  SegView v{q, &sp, seg, sp.filter, sp.num_filter_nodes};
-  // top-level AND children (node ranges [begin, end))
-  std::vector<std::pair<int, int>> kids;
+// The top-level AND children of a segment's filter in query order, split into the dense prefix (streamed) and the
+// residual rest (per candidate doc)
+struct ChildSplit {
+  std::vector<std::pair<int, int>> kids;  // node ranges [begin, end)
+  std::vector<double> sel;                // share of docs each child keeps (analyze)
+  std::vector<int> dense_kids, resid_kids, staged;
+  double rho = 1.0, rho_dense = 1.0;
+  bool residual = false;
+};
+bool split_children(const SegView& v, ChildSplit& cs) {
+  std::vector<std::pair<int, int>>& kids = cs.kids;
   if (v.n > 0) {
     double s;
     std::vector<int> scans;
     const int e = analyze(v, 0, &s, &scans);
-    if (e != v.n) return fail(PGPU_E_INVALID, "malformed filter program");
+    if (e != v.n) return false;
     if (v.nd[0].op == PGPU_F_AND_BEGIN) {
       int j = 1;
       while (v.nd[j].op != PGPU_F_AND_END) {
@@ -2306,31 +2376,148 @@ int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pg
     }
   }
   // dense prefix of the children: every scan column of a dense child is read with >= kDenseTouch sector density
-  double rho = 1.0, rho_dense = 1.0;
-  bool residual = false;
-  std::vector<int> dense_kids, resid_kids, staged;
-  auto add_stage = [&](int qc) {
-    if (std::find(staged.begin(), staged.end(), qc) == staged.end()) staged.push_back(qc);
-  };
   for (size_t k = 0; k < kids.size(); ++k) {
     double s;
     std::vector<int> scans;
     analyze(v, kids[k].first, &s, &scans);
-    bool dense = !residual;
+    bool dense = !cs.residual;
     for (int qc : scans)
-      if (dense && v.dev(qc)->kind == PGPU_COL_FIXED_BIT && sector_touch(rho, v.dev(qc)->bits) < kDenseTouch)
+      if (dense && v.dev(qc)->kind == PGPU_COL_FIXED_BIT && sector_touch(cs.rho, v.dev(qc)->bits) < kDenseTouch)
         dense = false;
     if (dense) {
-      dense_kids.push_back((int)k);
+      cs.dense_kids.push_back((int)k);
       for (int qc : scans)
-        if (v.dev(qc)->kind == PGPU_COL_FIXED_BIT) add_stage(qc);
+        if (v.dev(qc)->kind == PGPU_COL_FIXED_BIT && std::find(cs.staged.begin(), cs.staged.end(), qc) == cs.staged.end())
+          cs.staged.push_back(qc);
     } else {
-      residual = true;
-      resid_kids.push_back((int)k);
+      cs.residual = true;
+      cs.resid_kids.push_back((int)k);
     }
-    rho *= s;
-    if (dense) rho_dense *= s;
+    cs.sel.push_back(s);
+    cs.rho *= s;
+    if (dense) cs.rho_dense *= s;
   }
+  return true;
+}
+
+// A segment's lead leaf (lead_model): child `kid` of the top-level AND, streamed as the top P planes of its column
+struct LeadChoice {
+  int kid = -1;  // -1: the segment keeps its query order
+  int col = -1, bits = 0, P = 0;
+  int nr = 0;
+  uint32_t rng[PGPU_SLICE_RANGES][2] = {};
+  double today = 0, lead = 0;  // modelled bytes per tile
+};
+
+// The matching dict ids [a, b) of a child that is one non-negated SCAN node (RANGE, or a set convert_filter turns
+// into an inline LIST or a MASK, clamped as it clamps them) on a fixed-bit column of <= 31 bits with a bit-sliced
+// copy.  False for any other child.
+bool scan_runs(const SegView& v, const std::pair<int, int>& kid, std::vector<std::pair<uint64_t, uint64_t>>& runs) {
+  if (kid.second - kid.first != 1) return false;
+  const pgpu_filter_node& x = v.nd[kid.first];
+  if (x.op != PGPU_F_SCAN || x.negate) return false;
+  const DevColumn* dc = v.dev(x.column);
+  if (dc->kind != PGPU_COL_FIXED_BIT || !dc->sliced || dc->bits < 1 || dc->bits > 31) return false;
+  if (x.pred == PGPU_PRED_RANGE) {
+    const int64_t lo = std::max(0, x.lo), hi = std::min(x.hi, dc->card);
+    if (hi > lo) runs.emplace_back((uint64_t)lo, (uint64_t)hi);
+    return true;
+  }
+  if (x.pred != PGPU_PRED_SET || !(dc->card <= 64 || x.num_ids <= 8) || x.num_ids < 0 || (x.num_ids && !x.ids))
+    return false;
+  for (int j = 0; j < x.num_ids; ++j) {
+    if (x.ids[j] < 0 || x.ids[j] >= dc->card) return false;
+    runs.emplace_back((uint64_t)x.ids[j], (uint64_t)x.ids[j] + 1);
+  }
+  return true;
+}
+
+// Bytes per tile a segment in query order reads more once its launch streams no prefix planes (DevParams::rd_pfx
+// is one figure per launch, and a segment with a lead leaf has none): what plan_prefix's rule says they save
+double prefix_loss(const SegView& v) {
+  ChildSplit cs;
+  std::vector<std::pair<uint64_t, uint64_t>> runs;
+  if (!split_children(v, cs) || cs.resid_kids.size() != 1 || !scan_runs(v, cs.kids[cs.resid_kids[0]], runs)) return 0;
+  const int bits = v.dev(v.nd[cs.kids[cs.resid_kids[0]].first].column)->bits, K = PGPU_PFX_PLANES;
+  std::vector<std::pair<uint32_t, uint32_t>> m;
+  double cov;
+  if (bits <= K || !prefix_ranges(runs, bits, K, m, &cov)) return 0;
+  return std::max(0.0, cs.rho_dense * PGPU_WT * 128.0 * (1.0 - cov) - 256.0 * K);
+}
+
+// The later child of the segment's top-level AND with the cheapest lead plan, when there is one: a single non-negated
+// SCAN leaf (RANGE, or a set that becomes an inline LIST / MASK) on a fixed-bit column with a bit-sliced copy, every
+// other child made of SCAN leaves on fixed-bit columns only (gathered per candidate doc; bitmap, index and raw leaves
+// keep their place in the dense program).  Not whether it pays: pack_query decides that for the whole query.
+bool lead_choice(const SegView& v, LeadChoice* out) {
+  if (v.n < 6 || v.nd[0].op != PGPU_F_AND_BEGIN) return false;
+  // (first, and without the analysis below: queries with index, bitmap or raw leaves pay one pass over their nodes)
+  for (int i = 0; i < v.n; ++i) {
+    const pgpu_filter_node& x = v.nd[i];
+    const bool mark = x.op == PGPU_F_AND_BEGIN || x.op == PGPU_F_AND_CHILD_END || x.op == PGPU_F_AND_END ||
+                      x.op == PGPU_F_OR_BEGIN || x.op == PGPU_F_OR_CHILD_END || x.op == PGPU_F_OR_END ||
+                      x.op == PGPU_F_NOT;
+    if (!mark && !(x.op == PGPU_F_SCAN && x.column >= 0 && x.column < v.q->num_columns &&
+                   v.dev(x.column)->kind == PGPU_COL_FIXED_BIT))
+      return false;
+  }
+  ChildSplit cs;
+  if (!split_children(v, cs) || cs.kids.size() < 2) return false;
+  int bits_a = 0;
+  for (int qc : cs.staged) bits_a += v.dev(qc)->bits;
+  for (size_t k = 1; k < cs.kids.size(); ++k) {
+    std::vector<std::pair<uint64_t, uint64_t>> runs;
+    if (!scan_runs(v, cs.kids[k], runs)) continue;
+    const pgpu_filter_node& x = v.nd[cs.kids[k].first];
+    const DevColumn* dc = v.dev(x.column);
+    const bool was_dense = std::find(cs.dense_kids.begin(), cs.dense_kids.end(), (int)k) != cs.dense_kids.end();
+    const int kind = cs.resid_kids.empty() ? PGPU_LEAD_RESID_NONE
+                     : cs.resid_kids.size() == 1 && cs.resid_kids[0] == (int)k ? PGPU_LEAD_RESID_B
+                                                                                : PGPU_LEAD_RESID_OTHER;
+    pgpu_lead_model_out m;
+    lead_model(bits_a, cs.rho_dense, kind, (int)cs.dense_kids.size() - (was_dense ? 1 : 0), dc->bits, cs.sel[k], runs, &m);
+    if (!m.planes || (out->kid >= 0 && m.lead_bytes >= out->lead)) continue;
+    out->kid = (int)k;
+    out->col = x.column;
+    out->bits = dc->bits;
+    out->P = m.planes;
+    out->nr = m.num_ranges;
+    for (int r = 0; r < PGPU_SLICE_RANGES; ++r) out->rng[r][0] = m.ranges[r][0], out->rng[r][1] = m.ranges[r][1];
+    out->today = m.today_bytes;
+    out->lead = m.lead_bytes;
+  }
+  return out->kid >= 0;
+}
+
+int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pgpu_segment* seg,
+                 const DevParams& p, Packer& pk, DevSeg& ds, const LeadChoice* lead = nullptr) {
+  SegView v{q, &sp, seg, sp.filter, sp.num_filter_nodes};
+  ChildSplit cs;
+  if (!split_children(v, cs)) return fail(PGPU_E_INVALID, "malformed filter program");
+  const std::vector<std::pair<int, int>>& kids = cs.kids;
+  const double rho = cs.rho;
+  double rho_dense = cs.rho_dense;
+  bool residual = cs.residual;
+  std::vector<int> dense_kids = cs.dense_kids, resid_kids = cs.resid_kids, staged = cs.staged;
+  if (lead && lead->kid < 0) lead = nullptr;
+  if (lead) {
+    // the lead leaf alone is dense; residual: B exact (unless the lead leaf is), the former dense children in their
+    // order, then the former residual children in theirs
+    std::vector<int> r;
+    if (lead->P < lead->bits) r.push_back(lead->kid);
+    for (int k : dense_kids)
+      if (k != lead->kid) r.push_back(k);
+    for (int k : resid_kids)
+      if (k != lead->kid) r.push_back(k);
+    dense_kids.assign(1, lead->kid);
+    resid_kids = r;
+    staged.assign(1, lead->col);
+    residual = true;
+    rho_dense = cs.sel[lead->kid];
+  }
+  auto add_stage = [&](int qc) {
+    if (std::find(staged.begin(), staged.end(), qc) == staged.end()) staged.push_back(qc);
+  };
   const size_t nfilter_stage = staged.size();
   // aggregation plan
   std::vector<int> aggcols;
@@ -2444,7 +2631,8 @@ int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pg
   rc = convert_filter(q, sp, rn.data(), (int)rn.size(), seg, pk);
   if (rc) return rc;
   ds.rprog_len = (int32_t)pk.instrs.size() - ds.rprog_begin;
-  plan_prefix(v, pk, rho_dense, ds);
+  if (lead) ds.pfx_col = -1;  // (the lead leaf is the pre-filter)
+  else plan_prefix(v, pk, rho_dense, ds);
   auto stage_index = [&](int qc) {
     for (size_t j = 0; j < staged.size(); ++j)
       if (staged[j] == qc) return (int)j;
@@ -2469,6 +2657,14 @@ int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pg
     }
     if (ok && nscan >= 1 && (nand == 0 ? ds.prog_len == 1 : ds.prog_len == 2 * nscan + 2)) ds.fast = nscan;
   }
+  if (lead) {  // its one SCAN leaf (an inline LIST too: only its prefix ranges below are evaluated)
+    // (convert_filter folded the leaf, or its column was not staged: no error, the query keeps its order)
+    if (ds.prog_len != 1 || pk.instrs[ds.prog_begin].op != PGPU_I_SCAN || stage_index(lead->col) != 0)
+      return kLeadRetry;
+    ds.fast = 1;
+    ds.fast_ins[0] = 0;
+    ds.fast_ins[1] = -1;
+  }
   // bit-sliced fast leaves (kernel sliced_ranges): the column has a bit-sliced copy, only the dense filter reads
   // its staged tiles (it is not an aggregation / group column decoded from the slot, nor the other fast leaf's
   // column), and the predicate is a RANGE or a 64-id MASK whose ids (or their complement) form <= 4 runs
@@ -2477,7 +2673,14 @@ int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pg
     ds.f_nr[j] = ds.f_sneg[j] = 0;
     for (int r = 0; r < PGPU_SLICE_RANGES; ++r) ds.f_rng[j][r][0] = ds.f_rng[j][r][1] = 0;
   }
-  for (int j = 0; j < ds.fast; ++j) {
+  ds.f_plane0 = 0;
+  if (lead) {  // ranges of the top P id bits, on planes [bits - P, bits)
+    ds.f_plane0 = lead->bits - lead->P;
+    ds.f_nr[0] = lead->nr;
+    for (int r = 0; r < lead->nr; ++r) ds.f_rng[0][r][0] = lead->rng[r][0], ds.f_rng[0][r][1] = lead->rng[r][1];
+    ds.stage_sliced = 1;
+  }
+  for (int j = 0; j < (lead ? 0 : ds.fast); ++j) {
     const DevInstr& in = pk.instrs[ds.prog_begin + ds.fast_ins[j]];
     const DevColumn* dc = v.dev(in.col);
     if (!dc->sliced || dc->bits < 1 || dc->bits > 31) continue;
@@ -2691,7 +2894,17 @@ bool program_truth_table(const Packer& pk, DevSeg& ds) {
   return true;
 }
 
-int pack_query(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_layout& L, Packer& pk, DevParams& p) {
+// The query's lead-leaf decision (lead_model): made once per query from the sums over its segments -- the prefix
+// pre-filter is all-or-nothing per launch and a switched segment has none, so segments do not switch one by one
+struct LeadInfo {
+  bool allow = true;      // in: consider a switch
+  bool switched = false;  // out
+  int col = -1, P = 0;    // the first switched segment's lead column and planes
+  double today = 0, lead = 0;  // modelled bytes of the whole query
+};
+
+int pack_query(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_layout& L, Packer& pk, DevParams& p,
+               LeadInfo* li = nullptr) {
   memset(&p, 0, sizeof(p));
   p.ncols = q->num_columns;
   p.ngcols = q->num_group_columns;
@@ -2751,6 +2964,45 @@ int pack_query(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_lay
       return fail(PGPU_E_INVALID, "group column %d is multi-value in %d of %d segments", g, nmv, q->num_segments);
     if (nmv) p.mv_gmask |= 1 << g;
   }
+  // lead leaf: the segments that have one switch together when the query's tiles save enough by it; a segment that
+  // has none keeps its order and is charged the prefix planes it loses.  Not with exact filter statistics
+  // (query_kernel_rfsm needs both leaves in full) nor multi-value group keys (ring kernel only).
+  std::vector<LeadChoice> leads((size_t)std::max(0, q->num_segments));
+  if (li) li->switched = false;
+  const int64_t lead_thr = pgpu_lead_switch_bytes();
+  if (li && li->allow && lead_thr >= 0 && !(q->flags & PGPU_Q_EXACT_FILTER_STATS) && !p.mv_gmask) {
+    bool ok = true, any = false;
+    double today = 0, lead = 0;
+    for (int s = 0; s < q->num_segments && ok; ++s) {
+      const pgpu_segment_plan& sp = q->segments[s];
+      const pgpu_segment* seg = sp.segment;
+      // (a segment the loop below rejects -- missing, not sealed, a column mapped to no slot -- is reported there:
+      // nothing here reads through its column map first)
+      ok = seg && seg->sealed && (sp.column_map || !q->num_columns);
+      for (int c = 0; ok && c < q->num_columns; ++c)
+        ok = sp.column_map[c] >= 0 && sp.column_map[c] < (int32_t)seg->dev.size();
+      if (!ok) break;
+      SegView v{q, &sp, seg, sp.filter, sp.num_filter_nodes};
+      if (v.n == 1 && v.nd[0].op == PGPU_F_EMPTY) continue;  // no tiles
+      const double nt = (double)((seg->num_docs + PGPU_WT - 1) / PGPU_WT);
+      if (!lead_choice(v, &leads[s])) continue;
+      today += nt * leads[s].today;
+      lead += nt * leads[s].lead;
+      if (!any) li->col = leads[s].col, li->P = leads[s].P;
+      any = true;
+    }
+    // (only now, so that a query without any lead leaf has paid one look at each segment's nodes and no more)
+    for (int s = 0; s < q->num_segments && ok && any; ++s) {
+      const pgpu_segment_plan& sp = q->segments[s];
+      SegView v{q, &sp, sp.segment, sp.filter, sp.num_filter_nodes};
+      if (leads[s].kid >= 0 || (v.n == 1 && v.nd[0].op == PGPU_F_EMPTY)) continue;
+      lead += (double)((sp.segment->num_docs + PGPU_WT - 1) / PGPU_WT) * prefix_loss(v);
+    }
+    li->switched = ok && any && pgpu_lead_switch(today - lead, lead_thr);
+    li->today = today;
+    li->lead = lead;
+  }
+  const bool lead_on = li && li->switched;
   int64_t tiles = 0;
   for (int s = 0; s < q->num_segments; ++s) {
     const pgpu_segment_plan& sp = q->segments[s];
@@ -2790,7 +3042,7 @@ int pack_query(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_lay
         return fail(PGPU_E_UNSUPPORTED, "segment %d: aggregation over a multi-value column (use its row columns)", s);
       if (c.dict_type != L.agg_value_type[a]) return fail(PGPU_E_INVALID, "segment %d: agg column type differs", s);
     }
-    int rc = plan_segment(q, sp, seg, p, pk, ds);
+    int rc = plan_segment(q, sp, seg, p, pk, ds, lead_on ? &leads[s] : nullptr);
     if (rc) return rc;
     // a filter folded to EMPTY (a literal absent from the dictionary under an AND, ...) matches nothing: the
     // reference's EmptyFilterOperator scans no doc, so the segment gets no tiles
@@ -3059,8 +3311,9 @@ void try_rdirect(int num_cus, const Packer& pk, DevParams& p, LaunchPlan& pl) {
         continue;
       }
       const DevColumn& c = pk.cols[ds.col_begin + ds.stage_col[0]];
-      rd &= c.bits >= 1 && c.bits <= 16;
-      rd_bits = std::max(rd_bits, (int)c.bits);
+      const int planes = c.bits - ds.f_plane0;  // (a lead leaf: the top planes only)
+      rd &= planes >= 1 && planes <= 16;
+      rd_bits = std::max(rd_bits, planes);
     }
   const size_t rdyn = reg_kernel_lds(p);
   if (!rd || rdyn > PGPU_LDS_LIMIT) return;
@@ -3470,14 +3723,16 @@ void try_pscan(int num_cus, const pgpu_query_desc* q, const pgpu_table_layout& L
 }
 
 // PGPU_PLAN_TRACE=1: the kernel chosen and the plan of each segment, on stderr
-void trace_plan(const Packer& pk, const DevParams& p, const LaunchPlan& pl) {
+void trace_plan(const Packer& pk, const DevParams& p, const LaunchPlan& pl, const LeadInfo& li) {
+  char lead[96] = "";  // a switched query only: lead column, planes, modelled bytes today -> lead
+  if (li.switched) snprintf(lead, sizeof(lead), " lead col %d P %d bytes %.0f->%.0f", li.col, li.P, li.today, li.lead);
   fprintf(stderr, "[pgpu plan] mode %d dense %d direct %d pscan %d grid %d dyn %zu tiles %d units %d invx %zu "
           "rd_planes %d rd_pfx %d rs_vplanes %d dslots %d min_instrs %d ring_slots %d inflight %d rk_ids %d "
-          "rk_leaves %d pscan_kb %d pscan_vb %d pshift %d nparts %llu ldict %d rw %d rec_idbits %d nwaves %d\n",
+          "rk_leaves %d pscan_kb %d pscan_vb %d pshift %d nparts %llu ldict %d rw %d rec_idbits %d nwaves %d%s\n",
           p.mode, p.dense, p.direct, p.pscan, pl.grid, pl.dyn, p.total_tiles, p.total_units, pk.invx.size(),
           p.rd_planes, p.rd_pfx, p.rs_vplanes, p.dslots, p.min_instrs, p.ring_slots, p.inflight, p.rk_ids,
           p.rk_leaves, p.pscan_kb, p.pscan_vb, pl.pshift, (unsigned long long)pl.nparts, pl.ldict, pl.part_rw,
-          pl.part_idbits, pl.nwaves);
+          pl.part_idbits, pl.nwaves, lead);
   for (size_t i = 0; i < pk.segs.size(); ++i) {
     const DevSeg& ds = pk.segs[i];
     fprintf(stderr, "[pgpu plan]  seg %zu tiles %d prog %d (op %d) rprog %d agg_mode %d nstage %d fast %d sliced %d "
@@ -3510,7 +3765,32 @@ int plan_launch(int num_cus, const pgpu_query_desc* q, const pgpu_table_layout& 
   plan_part_records(q, L, p, pl);
   try_pscan(num_cus, q, L, pk, p, pl);  // PART: any -> ring + pscan (PGPU_KV_PSCAN), with the FOR geometry
   pl.nwaves = pl.grid * (p.direct != PGPU_KV_RING || p.pscan ? 4 : PGPU_WAVES_OF(p.dense));
-  if (plan_trace_on()) trace_plan(pk, p, pl);
+  return PGPU_OK;
+}
+
+// pack_query and plan_launch.  A lead-leaf switch (LeadInfo) is planned for query_kernel_rdirect only: when the
+// launch does not end on it (another condition of try_rdirect fails, PGPU_NO_RDIRECT, the LDS limit), or the lead
+// leaf did not pack as one staged SCAN (kLeadRetry), the query is packed again in query order, so that it runs
+// exactly the plan it would have without the switch.
+int pack_and_plan(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_layout& L, Packer& pk, DevParams& p,
+                  LaunchPlan& pl) {
+  LeadInfo li;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    pk = Packer();
+    pl = LaunchPlan();
+    li.allow = attempt == 0;
+    const double tp0 = HostTiming::us();
+    int rc = pack_query(ctx, q, L, pk, p, &li);
+    host_timing().add(2, tp0, HostTiming::us());
+    if (rc == kLeadRetry && attempt == 0) continue;  // a lead leaf that did not pack as one: query order
+    if (rc) return rc;
+    // host only: which kernel, grid and LDS size, and with them whether the query is one launch or three
+    drop_reference_replay(q, pk);
+    rc = plan_launch(ctx->num_cus, q, L, pk, p, pl);
+    if (rc) return rc;
+    if (!li.switched || p.direct == PGPU_KV_RDIRECT) break;
+  }
+  if (plan_trace_on()) trace_plan(pk, p, pl, li);
   return PGPU_OK;
 }
 
@@ -4118,6 +4398,35 @@ pgpu_query* make_query_handle(pgpu_context* ctx, const pgpu_query_desc* q, const
 
 extern "C" {
 
+static_assert(PGPU_SLICE_RANGES == 4, "pgpu_lead_model_out::ranges");
+int pgpu_lead_model(int32_t bits_a, double rho_dense, int32_t residual_kind, int32_t num_dense_scans, int32_t bits_b,
+                    double sel_b, const uint32_t* runs, int32_t num_runs, pgpu_lead_model_out* out) {
+  if (!out || num_runs < 0 || (num_runs && !runs)) return fail(PGPU_E_INVALID, "null argument");
+  if (bits_a < 0 || bits_b < 1 || bits_b > 31 || num_dense_scans < 0 || residual_kind < PGPU_LEAD_RESID_NONE ||
+      residual_kind > PGPU_LEAD_RESID_OTHER)
+    return fail(PGPU_E_INVALID, "lead model: bits %d / %d, residual kind %d", bits_a, bits_b, residual_kind);
+  std::vector<std::pair<uint64_t, uint64_t>> r;
+  for (int k = 0; k < num_runs; ++k) {
+    if (runs[2 * k + 1] <= runs[2 * k]) continue;
+    if (runs[2 * k + 1] > (1ull << bits_b)) return fail(PGPU_E_INVALID, "lead model: id run past 2^%d", bits_b);
+    r.emplace_back(runs[2 * k], runs[2 * k + 1]);
+  }
+  lead_model(bits_a, rho_dense, residual_kind, num_dense_scans, bits_b, sel_b, r, out);
+  return PGPU_OK;
+}
+
+int64_t pgpu_lead_switch_bytes(void) {
+  const char* v = getenv("PGPU_LEAD_SWITCH_BYTES");  // read per plan: tests
+  if (!v || !*v) return kLeadSwitchBytes;
+  char* end = nullptr;
+  const long long x = strtoll(v, &end, 10);
+  return end != v && *end == '\0' ? (int64_t)x : kLeadSwitchBytes;  // (a value that does not parse: the default)
+}
+
+int32_t pgpu_lead_switch(double saved_bytes, int64_t threshold_bytes) {
+  return threshold_bytes >= 0 && saved_bytes > 0 && saved_bytes >= (double)threshold_bytes;
+}
+
 // Every query enters the GPU here, as a sequence of phases: pack_query, drop_reference_replay, plan_launch and
 // split_reason (host only), then pick_stream, ensure_workspace, fill_arena, enqueue_fused or enqueue_split,
 // make_query_handle.
@@ -4141,14 +4450,8 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
                 (unsigned long long)need);
   Packer pk;
   DevParams p;
-  const double tp0 = HostTiming::us();
-  rc = pack_query(ctx, q, L, pk, p);
-  host_timing().add(2, tp0, HostTiming::us());
-  if (rc) return rc;
-  // host only: which kernel, grid and LDS size, and with them whether the query is one launch or three
-  drop_reference_replay(q, pk);
   LaunchPlan pl;
-  rc = plan_launch(ctx->num_cus, q, L, pk, p, pl);
+  rc = pack_and_plan(ctx, q, L, pk, p, pl);
   if (rc) return rc;
   TableTarget target{dev_table, host_table, eager, eager_order, tws};
   const char* split_why = split_reason(q, L, pk, p, pl, target);
