@@ -269,8 +269,9 @@ typedef struct {
 #define PGPU_AGG_MIN 2   /* MinAggregationFunction.java:55-138, empty = +inf */
 #define PGPU_AGG_MAX 3   /* MaxAggregationFunction.java:55-138, empty = -inf */
 #define PGPU_AGG_AVG 4   /* AvgAggregationFunction.java:58-190 + AvgPair */
-/* (fn values above PGPU_AGG_AVG are PGPU_E_UNSUPPORTED.  DISTINCTCOUNT is no descriptor function: it is a GROUP BY on
- * the column, folded at collect -- pgpu_query_collect_fold below.) */
+/* (fn values above PGPU_AGG_AVG are PGPU_E_UNSUPPORTED.  DISTINCTCOUNT and PERCENTILE are no descriptor functions:
+ * each is a GROUP BY on the column, folded at collect -- pgpu_query_collect_fold below -- and, for PERCENTILE, with the
+ * rank selected along the column's ids behind the fold -- pgpu_query_collect_select.) */
 
 typedef struct {
   int32_t fn;
@@ -566,6 +567,42 @@ int pgpu_table_fold(pgpu_context* ctx, const pgpu_table_layout* in_layout, const
 int pgpu_query_collect_fold(pgpu_query* query, uint64_t inner_keys, const pgpu_topk* order, int64_t* out_keys,
                             int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
                             pgpu_query_stats* out_stats, pgpu_table_layout* out_layout);
+
+/* ---- PERCENTILE: rank selection over the value axis of the same table ------------------------------------------
+ * PercentileAggregationFunction.java:82-100,152-165 collects every value of the column per group, sorts them and
+ * returns values[(int) ((long) size * percentile / 100)] (values[size - 1] at 100).  Global dictionaries are sorted,
+ * so section 0 of the table GROUP BY g_1..g_n, c -- the counts per (g, cid) -- is that sorted multiset, and the
+ * answer is the smallest cid whose running count along cid passes the rank.  With N_g the folded count of key g, in
+ * IEEE double and this operation order:
+ *   r = (p == 100) ? N_g - 1 : (int64) ((double) N_g * p / 100.0)      (at most N_g - 1: p within an ulp of 100)
+ *   selected cid = the smallest with  sum_{cid' <= cid} count(g, cid') > r
+ * The selected table is the folded table (pgpu_table_fold's nsec + 1 sections, bit for bit) followed by one int64
+ * section per percentile: section nsec + 1 + j holds, for key g, the cid selected for percentiles[j], 0 where the
+ * key's count is 0.  Every cell of those sections has one writer and the result does not depend on scheduling.
+ * pgpu_select_layout_of (host only) gives pgpu_fold_layout_of's layout plus those sections (PGPU_RED_SUM_I64), each
+ * also described as the next unused aggregation entry (PGPU_LONG, one part, exponent 0) like the distinct count:
+ * with n = the query's num_aggs the distinct count is entry n and percentile j entry n + 1 + j, so that
+ * pgpu_table_compact and pgpu_table_topk work unchanged and an order on percentile j is
+ * {PGPU_TOPK_AGG, PGPU_AGG_SUM, agg_index = n + 1 + j} -- ordering by cid is ordering by value.
+ *   PGPU_E_INVALID    : as pgpu_fold_layout_of; num_percentiles outside 1..PGPU_SELECT_MAX; (pgpu_table_select,
+ *                       pgpu_query_collect_select) a percentile outside [0, 100] or NaN
+ *   PGPU_E_UNSUPPORTED: as pgpu_fold_layout_of; no section or aggregation entry left for every percentile */
+#define PGPU_SELECT_MAX 8
+int pgpu_select_layout_of(const pgpu_table_layout* in, uint64_t inner_keys, int32_t num_percentiles,
+                          pgpu_table_layout* out);
+/* pgpu_table_fold followed by the selection, into caller memory `dev_out` (out_bytes >= pgpu_table_bytes of the
+ * selected layout), enqueued on `stream` without synchronising; the temporary memory comes from the context's pool in
+ * stream order.  Dense and one-word hash input as pgpu_table_fold takes them. */
+int pgpu_table_select(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
+                      uint64_t inner_keys, const double* percentiles, int32_t num_percentiles, void* dev_out,
+                      uint64_t out_bytes);
+/* pgpu_query_collect_fold with the selection behind the fold (no host round trip between them), for a query submitted
+ * with PGPU_Q_FOLD: `order` refers to the selected layout, out_cells is capacity x its num_sections.  A cancelled or
+ * expired query passes through with nothing folded or selected. */
+int pgpu_query_collect_select(pgpu_query* query, uint64_t inner_keys, const double* percentiles,
+                              int32_t num_percentiles, const pgpu_topk* order, int64_t* out_keys, int64_t* out_cells,
+                              uint64_t capacity, uint64_t* out_num_groups, pgpu_query_stats* out_stats,
+                              pgpu_table_layout* out_layout);
 
 /* Single-GPU asynchronous form (the combine operator of one server: BaseCombineOperator.getNextBlock submits the
  * segments' work and blocks in mergeResults, core/operator/combine/BaseCombineOperator.java:79-146):

@@ -725,10 +725,11 @@ class DistributedExecutor:
 
 def _refuse_distinct(query: QueryContext) -> None:
     """DISTINCTCOUNT across ranks needs the fold after the reduce (pgpu_table_fold on the reduced table), which the
-    multi-GPU combines do not do yet: the server keeps its CPU plan."""
-    if any(a.function == "DISTINCTCOUNT" for a in query.aggregations):
-        raise _lib.UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED,
-                                        "DISTINCTCOUNT is not served by the multi-GPU combine (DistributedExecutor)")
+    multi-GPU combines do not do yet: the server keeps its CPU plan.  PERCENTILE likewise (pgpu_table_select)."""
+    from .distinct import folded_names, has_distinct
+    if has_distinct(query):
+        raise _lib.UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED, f"{folded_names(query)} is not served by the "
+                                                                 "multi-GPU combine (DistributedExecutor)")
 
 
 class _DistPending:

@@ -70,6 +70,11 @@ hipError_t pgpu_gdict_encode(const uint64_t* keys, int64_t n, const uint64_t* un
 // fold of a group table over its last group column (pgpu_fold.hip)
 hipError_t pgpu_launch_fold(const int64_t* in, uint64_t N, int32_t nsec, const int32_t* ops, bool hash, uint64_t inner,
                             int64_t* out, int num_cus, hipStream_t st);
+// rank selection over the same axis, behind the fold (pgpu_select.hip)
+size_t pgpu_select_temp_bytes(uint64_t N, bool hash, uint64_t inner, int num_cus);
+hipError_t pgpu_launch_select(const int64_t* in, uint64_t N, int32_t nsec, bool hash, uint64_t inner,
+                              const double* percentiles, int32_t k, const int64_t* folded, int64_t* sel, void* temp,
+                              size_t temp_bytes, int num_cus, hipStream_t st);
 
 namespace {
 
@@ -304,6 +309,7 @@ struct Workspace {
   DevMem rkctab;                       // query_kernel_rkey: container record per (leaf, id, key)
   DevMem tk_keys, tk_state;            // pgpu_table_topk: per-row order keys, radix-select state + histogram
   DevMem fold;                         // pgpu_query_collect_fold: the folded table
+  DevMem sel_tmp;                      // pgpu_query_collect_select: chunk prefixes / sorted pairs of the selection
   PinnedMem h_arena, h_stats, h_total, h_table, h_segcnt, h_leafbits, h_segany, h_fsment;
   PinnedMem h_fold;                    // pgpu_query_collect_fold: a small folded table, compacted on the host
   DevMem d_cancel;                     // cancel word (DevParams::cancel): = the query's generation -> stop
@@ -4963,14 +4969,33 @@ int pgpu_table_fold(pgpu_context* ctx, const pgpu_table_layout* in_layout, const
   return PGPU_OK;
 }
 
-int pgpu_query_collect_fold(pgpu_query* qq, uint64_t inner_keys, const pgpu_topk* order, int64_t* out_keys,
-                            int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
-                            pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
+}  // extern "C"
+
+namespace {
+
+int check_percentiles(const double* percentiles, int32_t num_percentiles) {
+  if (num_percentiles < 1 || num_percentiles > PGPU_SELECT_MAX)
+    return fail(PGPU_E_INVALID, "%d percentiles (1..%d are selected at once)", num_percentiles, PGPU_SELECT_MAX);
+  if (!percentiles) return fail(PGPU_E_INVALID, "null argument");
+  for (int j = 0; j < num_percentiles; ++j)
+    if (!(percentiles[j] >= 0.0 && percentiles[j] <= 100.0))
+      return fail(PGPU_E_INVALID, "percentile %g is outside [0, 100]", percentiles[j]);
+  return PGPU_OK;
+}
+
+// pgpu_query_collect_fold (num_percentiles = 0) and pgpu_query_collect_select: the fold, the selection behind it on
+// the same stream, then the folded / selected table compacted or trimmed.
+int collect_folded(pgpu_query* qq, uint64_t inner_keys, const double* percentiles, int32_t num_percentiles,
+                   const pgpu_topk* order, int64_t* out_keys, int64_t* out_cells, uint64_t capacity,
+                   uint64_t* out_num_groups, pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
   if (!qq || !qq->tws || !out_num_groups) return fail(PGPU_E_INVALID, "query was not submitted");
   // (a cancelled or timed-out query returns here: nothing is folded)
   int rc = pgpu_query_wait(qq, out_stats);
   pgpu_table_layout F;
-  if (rc == PGPU_OK) rc = pgpu_fold_layout_of(&qq->layout, inner_keys, &F);
+  if (rc == PGPU_OK)
+    rc = num_percentiles ? pgpu_select_layout_of(&qq->layout, inner_keys, num_percentiles, &F)
+                         : pgpu_fold_layout_of(&qq->layout, inner_keys, &F);
+  if (rc == PGPU_OK && num_percentiles) rc = check_percentiles(percentiles, num_percentiles);
   if (rc == PGPU_OK) {
     // the table is complete (waited above): fold and compact it on the query's own workspace stream
     Workspace* ws = qq->ws;
@@ -4980,6 +5005,17 @@ int pgpu_query_collect_fold(pgpu_query* qq, uint64_t inner_keys, const pgpu_topk
       e = pgpu_launch_fold((const int64_t*)qq->tws->table.p, L.num_keys, L.num_sections, L.section_op,
                            L.key_kind == PGPU_KEYS_HASH, inner_keys, (int64_t*)ws->fold.p, qq->ctx->num_cus, ws->stream);
     if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table fold: %s", hipGetErrorString(e));
+    if (rc == PGPU_OK && num_percentiles) {
+      const bool hash = L.key_kind == PGPU_KEYS_HASH;
+      const size_t tb = pgpu_select_temp_bytes(L.num_keys, hash, inner_keys, qq->ctx->num_cus);
+      e = ws->sel_tmp.ensure(tb + 16, qq->ctx->mpool, ws->stream);
+      if (e == hipSuccess)
+        e = pgpu_launch_select((const int64_t*)qq->tws->table.p, L.num_keys, L.num_sections, hash, inner_keys,
+                               percentiles, num_percentiles, (const int64_t*)ws->fold.p,
+                               (int64_t*)ws->fold.p + (uint64_t)(L.num_sections + 1) * inner_keys, ws->sel_tmp.p, tb,
+                               qq->ctx->num_cus, ws->stream);
+      if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table select: %s", hipGetErrorString(e));
+    }
   }
   const bool trim = order && order->k > 0 && inner_keys > order->k;
   if (rc == PGPU_OK && !trim && pgpu_table_bytes(&F) <= (8u << 20)) {
@@ -5016,6 +5052,90 @@ int pgpu_query_collect_fold(pgpu_query* qq, uint64_t inner_keys, const pgpu_topk
   if (rc == PGPU_OK && out_layout) *out_layout = F;
   pgpu_query_release(qq);
   return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pgpu_query_collect_fold(pgpu_query* qq, uint64_t inner_keys, const pgpu_topk* order, int64_t* out_keys,
+                            int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
+                            pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
+  return collect_folded(qq, inner_keys, nullptr, 0, order, out_keys, out_cells, capacity, out_num_groups, out_stats,
+                        out_layout);
+}
+
+// ---- PERCENTILE: rank selection behind the fold (include/pinot_gpu.h; kernels in pgpu_select.hip) -------------------
+int pgpu_select_layout_of(const pgpu_table_layout* in, uint64_t inner_keys, int32_t num_percentiles,
+                          pgpu_table_layout* out) {
+  if (!in || !out) return fail(PGPU_E_INVALID, "null argument");
+  if (num_percentiles < 1 || num_percentiles > PGPU_SELECT_MAX)
+    return fail(PGPU_E_INVALID, "%d percentiles (1..%d are selected at once)", num_percentiles, PGPU_SELECT_MAX);
+  pgpu_table_layout F;
+  const int rc = pgpu_fold_layout_of(in, inner_keys, &F);
+  if (rc) return rc;
+  if (F.num_sections + num_percentiles > PGPU_MAX_SECTIONS)
+    return fail(PGPU_E_UNSUPPORTED, "no section left for %d percentiles (%d in use)", num_percentiles, F.num_sections);
+  // the distinct count took the first unused aggregation entry: the percentiles take the ones behind it
+  int n = 16;
+  while (n > 0 && F.agg_section[n - 1] == 0 && F.agg_value_type[n - 1] == 0) --n;
+  if (n + num_percentiles > 16)
+    return fail(PGPU_E_UNSUPPORTED, "no aggregation entry left for %d percentiles", num_percentiles);
+  for (int j = 0; j < num_percentiles; ++j) {
+    F.section_op[F.num_sections] = PGPU_RED_SUM_I64;
+    F.agg_section[n + j] = F.num_sections;
+    F.agg_value_type[n + j] = PGPU_LONG;
+    F.agg_sum_parts[n + j] = 1;
+    F.agg_sum_exp[n + j] = 0;
+    F.num_sections += 1;
+  }
+  *out = F;
+  return PGPU_OK;
+}
+
+int pgpu_table_select(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
+                      uint64_t inner_keys, const double* percentiles, int32_t num_percentiles, void* dev_out,
+                      uint64_t out_bytes) {
+  if (!ctx || !in_layout || !dev_table || !dev_out) return fail(PGPU_E_INVALID, "null argument");
+  pgpu_table_layout S;
+  int rc = pgpu_select_layout_of(in_layout, inner_keys, num_percentiles, &S);
+  if (rc == PGPU_OK) rc = check_percentiles(percentiles, num_percentiles);
+  if (rc) return rc;
+  if (out_bytes < pgpu_table_bytes(&S))
+    return fail(PGPU_E_INVALID, "selected table needs %llu bytes, %llu given", (unsigned long long)pgpu_table_bytes(&S),
+                (unsigned long long)out_bytes);
+  if (in_layout->num_keys == 0) return fail(PGPU_E_INVALID, "empty table");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const bool hash = in_layout->key_kind == PGPU_KEYS_HASH;
+  const int nsec = in_layout->num_sections;
+  HIP_TRY(pgpu_launch_fold((const int64_t*)dev_table, in_layout->num_keys, nsec, in_layout->section_op, hash,
+                           inner_keys, (int64_t*)dev_out, ctx->num_cus, st));
+  // the temporary memory is taken and given back in stream order: nothing waits for the kernels
+  const size_t tb = pgpu_select_temp_bytes(in_layout->num_keys, hash, inner_keys, ctx->num_cus);
+  void* temp = nullptr;
+  if (tb) {
+    if (ctx->mpool) HIP_TRY(hipMallocFromPoolAsync(&temp, tb, ctx->mpool, st));
+    else HIP_TRY(hipMallocAsync(&temp, tb, st));
+  }
+  const hipError_t e = pgpu_launch_select((const int64_t*)dev_table, in_layout->num_keys, nsec, hash, inner_keys,
+                                          percentiles, num_percentiles, (const int64_t*)dev_out,
+                                          (int64_t*)dev_out + (uint64_t)(nsec + 1) * inner_keys, temp, tb, ctx->num_cus,
+                                          st);
+  if (temp) (void)hipFreeAsync(temp, st);
+  if (e != hipSuccess) return fail(PGPU_E_HIP, "table select: %s", hipGetErrorString(e));
+  return PGPU_OK;
+}
+
+int pgpu_query_collect_select(pgpu_query* qq, uint64_t inner_keys, const double* percentiles, int32_t num_percentiles,
+                              const pgpu_topk* order, int64_t* out_keys, int64_t* out_cells, uint64_t capacity,
+                              uint64_t* out_num_groups, pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
+  if (num_percentiles < 1) {
+    // (never the plain fold by accident: the layout check refuses it after the wait, with the query released)
+    num_percentiles = -1;
+  }
+  return collect_folded(qq, inner_keys, percentiles, num_percentiles, order, out_keys, out_cells, capacity,
+                        out_num_groups, out_stats, out_layout);
 }
 
 }  // extern "C"

@@ -14,13 +14,19 @@ into the table ``GROUP BY g`` alone produces plus one section: the number of occ
 Several DISTINCTCOUNT columns run one pass each, all in flight together like the passes of FILTER clauses; the first
 carries ``A``, the others only COUNT(*); a column named twice is computed once.  The passes share the filter, so they
 meet the same groups and are joined on the group key.
+
+Exact PERCENTILE (PercentileAggregationFunction.java:82-100,152-165: every value of the column per group, sorted,
+``values[(int) ((long) size * percentile / 100)]``) rides the same passes: the global dictionary of ``c`` is sorted, so
+the counts of ``Q'`` along ``cid`` are that sorted multiset, and the device picks the smallest ``cid`` whose running
+count passes the rank behind the fold (pgpu_query_collect_select).  One pass per column carries DISTINCTCOUNT(c) and
+every percentile of ``c`` together -- one table, one fold, K picks; the final value is ``float(dictionary[cid])``.
 """
 from __future__ import annotations
 
 import copy
 import math
 import struct
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
 from . import _lib
@@ -29,10 +35,17 @@ from .query import MV_AGGS, AggregationSpec, OrderByExpr, QueryContext
 
 UNLIMITED = 1 << 62
 DISTINCT = "DISTINCTCOUNT"
+PERCENTILE = "PERCENTILE"
+FOLDED = (DISTINCT, PERCENTILE)  # the functions answered from the table folded over their column
 
 
 def has_distinct(query: QueryContext) -> bool:
-    return any(a.function == DISTINCT for a in query.aggregations)
+    return any(a.function in FOLDED for a in query.aggregations)
+
+
+def folded_names(query: QueryContext) -> str:
+    """The folded functions a query holds, for messages: 'DISTINCTCOUNT', 'PERCENTILE' or 'DISTINCTCOUNT / PERCENTILE'."""
+    return " / ".join(f for f in FOLDED if any(a.function == f for a in query.aggregations))
 
 
 def _unsupported(why: str) -> UnsupportedPlanError:
@@ -41,53 +54,65 @@ def _unsupported(why: str) -> UnsupportedPlanError:
 
 @dataclass
 class DistinctPass:
-    """One pass of a DISTINCTCOUNT query."""
+    """One pass of a DISTINCTCOUNT / PERCENTILE query."""
     query: QueryContext     # Q': GROUP BY g..., column with the pass's plain aggregations
     folded: QueryContext    # what the folded table answers: GROUP BY g... with Q's aggregations + DISTINCTCOUNT(column)
+                            # + the pass's percentiles (their cells hold the selected ids of column)
     column: str             # the folded column
     plain: List[int]        # original indexes of Q's aggregations, in their order ([]: Q' carries an inserted COUNT(*))
     distinct: List[int]     # original indexes of DISTINCTCOUNT(column) (every mention of it)
+    percentile: List[int] = field(default_factory=list)  # original indexes of PERCENTILE(column, p), one pick each
+
+    @property
+    def percentiles(self) -> List[float]:
+        """The pass's percentiles, in the order of its pick sections."""
+        return [a.percentile for a in self.folded.aggregations if a.function == PERCENTILE]
 
 
 def lower(query: QueryContext) -> List[DistinctPass]:
-    """The passes of a DISTINCTCOUNT query.  Raises UnsupportedPlanError for the combinations not served."""
+    """The passes of a DISTINCTCOUNT / PERCENTILE query.  Raises UnsupportedPlanError for the combinations not
+    served."""
     if not has_distinct(query):
-        raise ValueError("query has no DISTINCTCOUNT")
+        raise ValueError("query has no DISTINCTCOUNT or PERCENTILE")
+    what = folded_names(query)
     if query.has_filtered_aggregations:
-        raise _unsupported("DISTINCTCOUNT in a query with FILTER(WHERE ...) aggregations")
+        raise _unsupported(f"{what} in a query with FILTER(WHERE ...) aggregations")
     if any(a.function in MV_AGGS for a in query.aggregations):
-        raise _unsupported("DISTINCTCOUNT together with *MV aggregations")
-    plain = [i for i, a in enumerate(query.aggregations) if a.function != DISTINCT]
-    by_col: Dict[str, List[int]] = {}
+        raise _unsupported(f"{what} together with *MV aggregations")
+    plain = [i for i, a in enumerate(query.aggregations) if a.function not in FOLDED]
+    by_col: Dict[str, Tuple[List[int], List[int]]] = {}
     for i, a in enumerate(query.aggregations):
-        if a.function == DISTINCT:
+        if a.function in FOLDED:
             if a.column in query.group_by:
-                raise _unsupported(f"DISTINCTCOUNT of the group column {a.column!r}")
-            by_col.setdefault(a.column, []).append(i)
+                raise _unsupported(f"{a.function} of the group column {a.column!r}")
+            by_col.setdefault(a.column, ([], []))[a.function == PERCENTILE].append(i)
     passes = []
-    for k, (col, idx) in enumerate(by_col.items()):
+    for k, (col, (idx, pidx)) in enumerate(by_col.items()):
+        if len(pidx) > _lib.PGPU_SELECT_MAX:
+            raise _unsupported(f"{len(pidx)} percentiles of {col!r} (at most {_lib.PGPU_SELECT_MAX} per column)")
         mine = plain if k == 0 else []
         aggs = [query.aggregations[i] for i in mine] or [AggregationSpec("COUNT", None)]
         groups = list(query.group_by)
         low = QueryContext(table=query.table, select=groups + [col] + aggs, aggregations=list(aggs),
                            filter=query.filter, group_by=groups + [col], order_by=[], limit=UNLIMITED,
                            options=dict(query.options))
-        faggs = list(aggs) + [AggregationSpec(DISTINCT, col)]
+        faggs = list(aggs) + [AggregationSpec(DISTINCT, col)] + [query.aggregations[i] for i in pidx]
         folded = QueryContext(table=query.table, select=groups + faggs, aggregations=faggs, filter=query.filter,
                               group_by=groups, order_by=[], limit=UNLIMITED, options=dict(query.options))
-        passes.append(DistinctPass(low, folded, col, list(mine), idx))
+        passes.append(DistinctPass(low, folded, col, list(mine), idx, pidx))
     return passes
 
 
 def order_pass(query: QueryContext, passes: Sequence[DistinctPass]) -> Optional[Tuple[int, OrderByExpr]]:
     """(pass, expression) the server's ORDER BY trim selects by: the first ORDER BY expression, in the pass whose folded
-    table holds it -- a group column or a plain aggregation in the first pass, DISTINCTCOUNT(c) in c's pass.  The other
-    passes return every group; the join keeps the groups every pass returned."""
+    table holds it -- a group column or a plain aggregation in the first pass, DISTINCTCOUNT(c) or a percentile of c in
+    c's pass (its cell is the selected id of c: the order of the ids is the order of the values).  The other passes
+    return every group; the join keeps the groups every pass returned."""
     if not query.group_by or not query.order_by:
         return None
     ob = query.order_by[0]
     for pi, p in enumerate(passes):
-        if ob.expression == f"{DISTINCT.lower()}({p.column})":
+        if any(ob.expression == a.result_name for a in p.folded.aggregations if a.function in FOLDED):
             return pi, ob
     return 0, ob
 
@@ -106,17 +131,23 @@ def _join_stats(query: QueryContext, results: Sequence):
 
 
 def raise_result(query: QueryContext, passes: Sequence[DistinctPass], results: Sequence):
-    """The original query's QueryResult from the passes' folded results (QueryResults of ``DistinctPass.folded``)."""
+    """The original query's QueryResult from the passes' folded results (QueryResults of ``DistinctPass.folded``; a pass
+    with percentiles carries the global dictionary of its column as ``value_dictionary``)."""
     from .plan import QueryResult, order_and_limit, to_select_order
 
     res = QueryResult(query=query, stats=_join_stats(query, results))
     na = len(query.aggregations)
+    dicts = {id(p): r.value_dictionary for p, r in zip(passes, results) if p.percentile}
 
     def place(fin: list, p: DistinctPass, vals: Sequence) -> None:
         for j, i in enumerate(p.plain):
             fin[i] = vals[j]
+        nd = len(vals) - 1 - len(p.percentile)  # plain aggregations, then the distinct count, then the picks
         for i in p.distinct:
-            fin[i] = int(vals[-1])  # ColumnDataType.INT (DistinctCountAggregationFunction.java:303-310)
+            fin[i] = int(vals[nd])  # ColumnDataType.INT (DistinctCountAggregationFunction.java:303-310)
+        for j, i in enumerate(p.percentile):
+            # DOUBLE; no value met: DEFAULT_FINAL_RESULT (PercentileAggregationFunction.java:152-165)
+            fin[i] = float(dicts[id(p)][int(vals[nd + 1 + j])]) if int(vals[nd]) > 0 else -math.inf
 
     if not query.group_by:
         fin: list = [None] * na

@@ -156,10 +156,12 @@ class GpuNode:
 
 def _refuse_distinct(query: QueryContext) -> None:
     """DISTINCTCOUNT on a node needs the fold after the devices' tables are merged (pgpu_table_fold on the merged
-    table), which pgpu_node_collect does not do yet: the server keeps its CPU plan."""
-    if any(a.function == "DISTINCTCOUNT" for a in query.aggregations):
+    table), which pgpu_node_collect does not do yet: the server keeps its CPU plan.  PERCENTILE likewise
+    (pgpu_table_select)."""
+    from .distinct import folded_names, has_distinct
+    if has_distinct(query):
         raise _lib.UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED,
-                                        "DISTINCTCOUNT is not served by the node-level combine (GpuNode)")
+                                        f"{folded_names(query)} is not served by the node-level combine (GpuNode)")
 
 
 class _NodePending:

@@ -42,6 +42,7 @@ from ._lib import (ExprNode, Literal, PGPU_AGG_AVG, PGPU_AGG_COUNT, PGPU_AGG_MAX
 from .predicate import (DictPredicateEvaluator, RawPredicateEvaluator, SortedDictionary, get_predicate_evaluator,
                         get_raw_predicate_evaluator)
 from .query import MV_AGGS, UNBOUNDED, AggregationSpec, FilterContext, QueryContext, split_filtered_aggregations
+from .distinct import FOLDED, folded_names, has_distinct
 from .segment import DOCID_COLUMN, GpuContext, GpuSegment
 
 AGG_FN = {"COUNT": PGPU_AGG_COUNT, "SUM": PGPU_AGG_SUM, "MIN": PGPU_AGG_MIN, "MAX": PGPU_AGG_MAX,
@@ -330,6 +331,7 @@ class QueryResult:
         self._columns: Optional["GroupColumns"] = None
         self._group_rows: Optional[List[tuple]] = None
         self._intermediate: Optional[dict] = None
+        self.value_dictionary = None  # a folded pass with percentiles: the global dictionary of the folded column
 
     @property
     def group_rows(self) -> Optional[List[tuple]]:
@@ -341,9 +343,11 @@ class QueryResult:
     @property
     def intermediate(self) -> Optional[dict]:
         """group values -> intermediate values (AVG as (sum, count))."""
-        if any(a.function == "DISTINCTCOUNT" for a in self.query.aggregations):
-            # the broker-mergeable form of DISTINCTCOUNT is the value set, which the folded table no longer holds
-            raise UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED, "no intermediate result for a DISTINCTCOUNT query")
+        if has_distinct(self.query):
+            # the broker-mergeable form of DISTINCTCOUNT is the value set and that of PERCENTILE the value list, which
+            # the folded table no longer holds
+            raise UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED,
+                                       f"no intermediate result for a {folded_names(self.query)} query")
         if self._intermediate is None and self._columns is not None:
             self._intermediate = self._columns.intermediate()
         return self._intermediate
@@ -388,7 +392,9 @@ def final_value(fn: str, cell_count: int, cell: Optional[int], op: int, vtype: i
     """AggregationFunction.extractFinalResult on a merged cell (an exact Python int for integer sums)."""
     if fn == "COUNT":
         return int(cell_count)
-    if fn == "DISTINCTCOUNT":  # the appended section of a folded table (pgpu_fold_layout_of)
+    if fn in FOLDED:
+        # the appended sections of a folded table (pgpu_fold_layout_of / pgpu_select_layout_of): the distinct count,
+        # and per percentile the selected id of the folded column (distinct.raise_result turns it into the value)
         return int(cell)
     if fn == "SUM":
         return float(cell) if op == PGPU_RED_SUM_I64 else float(np.int64(cell).view(np.float64))
@@ -449,8 +455,8 @@ def topk_spec(query: QueryContext, cards: Sequence[int], k: int, key_base: int =
     else:
         t.source, t.agg_index = _lib.PGPU_TOPK_AGG, i - ng
         fn = query.aggregations[i - ng].function
-        # (a folded table's distinct count is a LONG SUM section: pgpu_fold_layout_of)
-        t.agg_fn = PGPU_AGG_SUM if fn == "DISTINCTCOUNT" else AGG_FN[fn]
+        # (a folded table's distinct count and selected ids are LONG SUM sections: pgpu_select_layout_of)
+        t.agg_fn = PGPU_AGG_SUM if fn in FOLDED else AGG_FN[fn]
     return t
 
 
@@ -873,10 +879,14 @@ class GpuPlanMaker:
         limit applies to the group keys only (the distinct sets are unbounded), so the lowered passes run without a
         limit, and neither the first-seen cut nor numGroupsLimitReached may then be possible."""
         check_group_columns(query, segments)
+        what = folded_names(query)
         for p in passes:
             if segments and segments[0].column(p.column).is_mv:
                 raise UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED,
-                                           f"DISTINCTCOUNT over the multi-value column {p.column!r}")
+                                           f"{what} over the multi-value column {p.column!r}")
+            if p.percentile and any(s.column(p.column).data_type == _lib.PGPU_STRING for s in segments):
+                raise UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED,
+                                           f"PERCENTILE over the STRING column {p.column!r}")
         if query.group_by and self.num_groups_limit > 0:
             for s in segments:
                 space = 1
@@ -885,7 +895,7 @@ class GpuPlanMaker:
                 if space >= self.num_groups_limit:
                     raise UnsupportedPlanError(
                         _lib.PGPU_E_UNSUPPORTED,
-                        f"DISTINCTCOUNT with a group key space of {space} in segment {s.name!r}: not below "
+                        f"{what} with a group key space of {space} in segment {s.name!r}: not below "
                         f"numGroupsLimit {self.num_groups_limit}")
 
     def submit_distinct(self, query: QueryContext, segments: Sequence[GpuSegment]) -> "DistinctPending":
@@ -909,6 +919,7 @@ class GpuPlanMaker:
         for p, (prep, inner, F, order) in zip(passes, ready):
             pq = self._launch(prep, segments)
             pq.fold = (inner, F, p.folded)
+            pq.percentiles = p.percentiles
             pq.order = order
             pending.append(pq)
         return DistinctPending(self, query, passes, pending)
@@ -925,7 +936,10 @@ class GpuPlanMaker:
             for g in globals_[:-1]:
                 inner *= len(g[0])
             F = TableLayout()
-            _lib.check(self.ctx._lib.pgpu_fold_layout_of(C.byref(L), inner, C.byref(F)))
+            if p.percentile:  # the folded table plus one section of selected ids per percentile
+                _lib.check(self.ctx._lib.pgpu_select_layout_of(C.byref(L), inner, len(p.percentile), C.byref(F)))
+            else:
+                _lib.check(self.ctx._lib.pgpu_fold_layout_of(C.byref(L), inner, C.byref(F)))
             order = None
             if op is not None and op[0] == pi:
                 # the trim's order over the folded table: its aggregation entries are Q's, then the distinct count
@@ -994,7 +1008,15 @@ class GpuPlanMaker:
         h, pending.handle = pending.handle, None
         query = pending.query
         order = pending.order
-        if fold is not None:
+        if fold is not None and pending.percentiles:  # ... and its percentiles picked behind the fold
+            query = fold[2]
+            ps = (C.c_double * len(pending.percentiles))(*pending.percentiles)
+            _lib.check(self.ctx._lib.pgpu_query_collect_select(h, fold[0], ps, len(ps),
+                                                               C.byref(order) if order is not None else None,
+                                                               keys.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                               cells.ctypes.data_as(C.POINTER(C.c_int64)), cap,
+                                                               C.byref(n), C.byref(st), None))
+        elif fold is not None:
             query = fold[2]
             _lib.check(self.ctx._lib.pgpu_query_collect_fold(h, fold[0], C.byref(order) if order is not None else None,
                                                              keys.ctypes.data_as(C.POINTER(C.c_int64)),
@@ -1018,7 +1040,11 @@ class GpuPlanMaker:
                                segment_matched=pending.matched[:pending.num_segments].copy(),
                                kernel_variant=st.kernel_variant)
         gdicts = [g[0] for g in pending.globals_]
-        return finish(query, table, gdicts[:-1] if fold is not None else gdicts, stats)
+        if fold is None:
+            return finish(query, table, gdicts, stats)
+        res = finish(query, table, gdicts[:-1], stats)
+        res.value_dictionary = gdicts[-1]
+        return res
 
     def execute(self, query: QueryContext, segments: Sequence[GpuSegment]) -> QueryResult:
         if has_distinct(query):
@@ -1137,7 +1163,8 @@ class PendingQuery:
     mv: Optional[tuple] = None  # (original query, lowered aggregation indexes) when *MV aggregations were lowered
     matched: Optional[np.ndarray] = None  # per-segment matched flags, filled by the wait (pgpu_query_matched_segments)
     order: Optional[object] = None  # the pgpu_topk given at submit (collect passes the same one)
-    fold: Optional[tuple] = None  # a DISTINCTCOUNT pass: (inner keys, folded layout, folded query) for collect
+    fold: Optional[tuple] = None  # a folded (DISTINCTCOUNT / PERCENTILE) pass: (inner keys, folded layout, folded query)
+    percentiles: Optional[list] = None  # ... and the percentiles picked behind its fold (pgpu_query_collect_select)
 
     def cancel(self) -> None:
         """Stop the query (pgpu_query_cancel): its kernels skip their remaining tiles and collect raises
@@ -1359,7 +1386,7 @@ class GroupColumns:
         s = None
         if fn == "COUNT":
             f = cnt.astype(np.int64)
-        elif fn == "DISTINCTCOUNT":
+        elif fn in FOLDED:
             f = cell.astype(np.int64)
         elif fn in ("SUM", "AVG") and L.agg_sum_parts[ai] > 1:
             # split sum: join the parts exactly (Python ints), round once to double (fixed point: times 2^exp)
@@ -1420,7 +1447,8 @@ class GroupColumns:
         parts = [self.value(gi, idx).tolist() for gi in range(len(self.global_dicts))]
         for ai, a in enumerate(self.query.aggregations):
             f = self.final(ai, idx)[0]
-            parts.append([int(x) for x in f.tolist()] if a.function in ("COUNT", "DISTINCTCOUNT") else f.tolist())
+            parts.append([int(x) for x in f.tolist()] if a.function in ("COUNT",) + FOLDED
+                         else f.tolist())
         return [tuple(r) for r in zip(*parts)] if parts else []
 
     def intermediate(self) -> dict:
@@ -1453,10 +1481,6 @@ def mv_lower(query: QueryContext):
 def mv_raise(query: QueryContext, parts, low_res):
     from .mv import raise_result
     return raise_result(query, parts, low_res)
-
-
-def has_distinct(query: QueryContext) -> bool:
-    return any(a.function == "DISTINCTCOUNT" for a in query.aggregations)
 
 
 def distinct_lower(query: QueryContext):

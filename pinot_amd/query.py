@@ -46,14 +46,33 @@ class FilterContext:
 
 @dataclass(frozen=True)
 class AggregationSpec:
-    function: str        # COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT; COUNTMV, SUMMV, MINMV, MAXMV, AVGMV (multi-value columns)
+    function: str        # COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT, PERCENTILE; COUNTMV, SUMMV, MINMV, MAXMV, AVGMV
+                         # (multi-value columns)
     column: Optional[str]  # None for COUNT(*)
     filter_key: Optional[str] = None  # FILTER(WHERE ...) clause text; its FilterContext is QueryContext.agg_filters
+    percentile: Optional[float] = None  # PERCENTILE only: 0..100
+    percentile_arg: bool = False        # written PERCENTILE(col, p), not PERCENTILE<N>(col): the result's name differs
 
     @property
     def result_name(self) -> str:
+        if self.function == "PERCENTILE":  # PercentileAggregationFunction.java:65-70
+            if self.percentile_arg:
+                return f"percentile({self.column}, {java_double_string(self.percentile)})"
+            return f"percentile{int(self.percentile)}({self.column})"
         name = f"{self.function.lower()}({self.column if self.column else '*'})"
         return name if self.filter_key is None else f"{name} FILTER(WHERE {self.filter_key})"
+
+
+def java_double_string(x: float) -> str:
+    """Java's Double.toString of a percentile (0..100, as the parser admits): the shortest round-trip digits, in plain
+    notation from 1e-3 up and as d.dddE-n below."""
+    x = float(x)
+    if x == 0 or x >= 1e-3:
+        return repr(x)
+    from decimal import Decimal
+    _, digits, exp = Decimal(repr(x)).normalize().as_tuple()  # (repr gives the shortest round-trip digits too)
+    ds = "".join(map(str, digits))
+    return f"{ds[0]}.{ds[1:] or '0'}E{len(ds) - 1 + exp}"
 
 
 @dataclass(frozen=True)
@@ -119,6 +138,7 @@ class QueryContext:
 _TOKEN = re.compile(r"\s*(?:(?P<num>-?\d+(?:\.\d+)?(?:[eE][-+]?\d+)?)|(?P<str>'(?:[^']|'')*')|"
                     r"(?P<op><>|!=|<=|>=|=|<|>|\(|\)|,|\*)|(?P<id>[A-Za-z_][A-Za-z0-9_.$]*))")
 _AGGS = {"COUNT", "SUM", "MIN", "MAX", "AVG", "DISTINCTCOUNT", "COUNTMV", "SUMMV", "MINMV", "MAXMV", "AVGMV"}
+_PERCENTILE = re.compile(r"^PERCENTILE(EST|TDIGEST|RAWEST|RAWTDIGEST|RAW)?(\d*)(MV)?$", re.IGNORECASE)
 MV_AGGS = {"COUNTMV": "COUNT", "SUMMV": "SUM", "MINMV": "MIN", "MAXMV": "MAX", "AVGMV": "AVG"}
 
 
@@ -191,6 +211,9 @@ class _Parser:
         t, t2 = self.peek(), self.peek(1)
         if t[0] == "id" and t[1].upper() == "DISTINCTCOUNTMV" and t2 == ("op", "("):
             raise SqlError("DISTINCTCOUNTMV is not supported (DISTINCTCOUNT over single-value columns only)")
+        pm = _PERCENTILE.match(t[1]) if t[0] == "id" and t2 == ("op", "(") else None
+        if pm:
+            return self.percentile_item(t[1].upper(), pm)
         if t[0] == "id" and t[1].upper() in _AGGS and t2 == ("op", "("):
             fn = t[1].upper()
             self.i += 2
@@ -216,6 +239,37 @@ class _Parser:
                 self.agg_filters[key] = f
             return AggregationSpec(fn, None if fn == "COUNT" else col, key)
         return self.ident()
+
+    def percentile_item(self, name: str, pm) -> AggregationSpec:
+        """PERCENTILE<N>(col) with one or two digits, or PERCENTILE(col, p) with p a number or a quoted number in
+        0..100 (AggregationFunctionFactory's two forms of the exact percentile)."""
+        sketch, digits, mv = pm.group(1), pm.group(2), pm.group(3)
+        if sketch:
+            raise SqlError(f"{name} is not supported (PERCENTILE{sketch.upper()} is a sketch or a raw form: only the "
+                           "exact PERCENTILE is served)")
+        if mv:
+            raise SqlError(f"{name} is not supported (PERCENTILE over single-value columns only)")
+        if len(digits) > 2:
+            raise SqlError(f"{name}: PERCENTILE<N> takes one or two digits; write PERCENTILE(col, p)")
+        self.i += 2
+        col = self.ident()
+        if digits:
+            p, arg = float(int(digits)), False
+        else:
+            self.expect_op(",")
+            lit = self.literal()
+            try:
+                p = float(lit)
+            except ValueError:
+                raise SqlError(f"PERCENTILE: {lit!r} is not a number") from None
+            if not 0.0 <= p <= 100.0:  # (NaN fails both comparisons)
+                raise SqlError(f"PERCENTILE: percentile {lit} is outside 0..100")
+            arg = True
+        self.expect_op(")")
+        nxt = self.peek()
+        if nxt[0] == "id" and nxt[1].upper() == "FILTER":
+            raise SqlError("PERCENTILE with FILTER(WHERE ...) is not supported")
+        return AggregationSpec("PERCENTILE", col, None, p, arg)
 
     def order_item(self) -> OrderByExpr:
         item = self.select_item()
