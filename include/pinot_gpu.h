@@ -271,7 +271,8 @@ typedef struct {
 #define PGPU_AGG_AVG 4   /* AvgAggregationFunction.java:58-190 + AvgPair */
 /* (fn values above PGPU_AGG_AVG are PGPU_E_UNSUPPORTED.  DISTINCTCOUNT and PERCENTILE are no descriptor functions:
  * each is a GROUP BY on the column, folded at collect -- pgpu_query_collect_fold below -- and, for PERCENTILE, with the
- * rank selected along the column's ids behind the fold -- pgpu_query_collect_select.) */
+ * rank selected along the column's ids behind the fold -- pgpu_query_collect_select.  MODE likewise, with the largest
+ * count along the column's ids found behind the fold -- pgpu_query_collect_mode.) */
 
 typedef struct {
   int32_t fn;
@@ -603,6 +604,54 @@ int pgpu_query_collect_select(pgpu_query* query, uint64_t inner_keys, const doub
                               int32_t num_percentiles, const pgpu_topk* order, int64_t* out_keys, int64_t* out_cells,
                               uint64_t capacity, uint64_t* out_num_groups, pgpu_query_stats* out_stats,
                               pgpu_table_layout* out_layout);
+
+/* ---- MODE: the most frequent value over the value axis of the same table -----------------------------------------
+ * ModeAggregationFunction.java:463-672 keeps a value -> count map per group and, at the end, returns the value of the
+ * largest count; where several values share it, MultiModeReducerType (:59-75) picks the smallest (MIN, the default),
+ * the largest (MAX) or their mean (AVG: the sum of the tied values, each converted to double before it is added,
+ * over their number).  Section 0 of the table GROUP BY g_1..g_n, c -- the counts per (g, cid) -- is that map over the
+ * ids of c's sorted global dictionary, so one reduction along cid behind the fold gives, per key g, five cells:
+ *   M   int64    the largest count(g, cid)
+ *   T   int64    the number of tied ids: those with count(g, cid) = M > 0
+ *   LO  int64    the smallest tied id  -- MODE(c, 'MIN') = value[LO]
+ *   HI  int64    the largest tied id   -- MODE(c, 'MAX') = value[HI]
+ *   S   float64  the sum of values[cid] over the tied ids -- MODE(c, 'AVG') = S / T; only with PGPU_MODE_AVG
+ * all 0 for a key no cell of which has a count > 0 (the reference's DEFAULT_FINAL_RESULT, -inf, is the caller's).
+ * Counts are compared as int64.  M, T, LO and HI do not depend on scheduling.  On dense input S does not either
+ * (one writer per cell, adds in an order the launch geometry fixes); on hash input it is accumulated with float64
+ * atomics and is exact up to the order of its adds.
+ * pgpu_mode_layout_of (host only) gives pgpu_select_layout_of's layout (num_percentiles > 0) or pgpu_fold_layout_of's
+ * (num_percentiles = 0) followed by the int64 sections M, T, LO, HI (PGPU_RED_SUM_I64) and, with PGPU_MODE_AVG in
+ * `reducers`, the float64 section S (PGPU_RED_SUM_F64).  LO and HI are also described as the next two unused
+ * aggregation entries (PGPU_LONG, one part, exponent 0) like the percentiles, so that pgpu_table_compact and
+ * pgpu_table_topk work unchanged and an order on MODE(c) / MODE(c, 'MAX') is {PGPU_TOPK_AGG, PGPU_AGG_SUM, agg_index
+ * = that entry} -- ordering by cid is ordering by value.  M, T and S are sections only.
+ *   PGPU_E_INVALID    : as pgpu_fold_layout_of / pgpu_select_layout_of; reducers = 0 or with bits other than the three
+ *                       below; (pgpu_table_mode, pgpu_query_collect_mode) PGPU_MODE_AVG without values
+ *   PGPU_E_UNSUPPORTED: as pgpu_fold_layout_of / pgpu_select_layout_of; no section or aggregation entry left */
+#define PGPU_MODE_MIN 1
+#define PGPU_MODE_MAX 2
+#define PGPU_MODE_AVG 4
+int pgpu_mode_layout_of(const pgpu_table_layout* in, uint64_t inner_keys, int32_t num_percentiles, int32_t reducers,
+                        pgpu_table_layout* out);
+/* pgpu_table_fold, the selection when num_percentiles > 0 (pgpu_table_select), and the mode reduction, into caller
+ * memory `dev_out` (out_bytes >= pgpu_table_bytes of the mode layout), enqueued on `stream` without synchronising; the
+ * temporary memory comes from the context's pool in stream order.  dev_values = `num_values` doubles in DEVICE memory,
+ * the value of every cid (ModeAggregationFunction.java:640-672's keys as doubles); required only with PGPU_MODE_AVG,
+ * NULL otherwise.  It is read at min(cid, num_values - 1): never outside, whatever the table holds.  Dense and
+ * one-word hash input as pgpu_table_fold takes them. */
+int pgpu_table_mode(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
+                    uint64_t inner_keys, const double* percentiles, int32_t num_percentiles, int32_t reducers,
+                    const double* dev_values, uint64_t num_values, void* dev_out, uint64_t out_bytes);
+/* pgpu_query_collect_select (num_percentiles = 0: pgpu_query_collect_fold) with the mode reduction behind it on the
+ * workspace stream, no host round trip between them -- the per-group map and final loop of
+ * ModeAggregationFunction.java:463-672.  `values` is HOST memory (num_values doubles), read before the call returns.
+ * `order` refers to the mode layout, out_cells is capacity x its num_sections.  A cancelled or expired query passes
+ * through with nothing folded, selected or reduced. */
+int pgpu_query_collect_mode(pgpu_query* query, uint64_t inner_keys, const double* percentiles, int32_t num_percentiles,
+                            int32_t reducers, const double* values, uint64_t num_values, const pgpu_topk* order,
+                            int64_t* out_keys, int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
+                            pgpu_query_stats* out_stats, pgpu_table_layout* out_layout);
 
 /* Single-GPU asynchronous form (the combine operator of one server: BaseCombineOperator.getNextBlock submits the
  * segments' work and blocks in mergeResults, core/operator/combine/BaseCombineOperator.java:79-146):

@@ -47,6 +47,7 @@ PGPU_MAX_FIXED_PARTS = 6  # widest fixed-point window (21-bit parts) of a floati
 PGPU_FIXED_TOL_BITS = 40
 PGPU_FOLD_MAX_KEYS = 1 << 26  # most inner keys of a fold (pgpu_fold_layout_of)
 PGPU_SELECT_MAX = 8  # most percentiles of one selection (pgpu_select_layout_of)
+PGPU_MODE_MIN, PGPU_MODE_MAX, PGPU_MODE_AVG = 1, 2, 4  # reducer mask of a mode reduction (pgpu_mode_layout_of)
 ABI_VERSION = 13
 
 
@@ -232,6 +233,14 @@ SIGNATURES = [
     ("pgpu_query_collect_select", C.c_int, [_P, C.c_uint64, C.POINTER(C.c_double), C.c_int32, C.POINTER(TopK),
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_uint64,
                                             C.POINTER(C.c_uint64), C.POINTER(QueryStats), C.POINTER(TableLayout)]),
+    ("pgpu_mode_layout_of", C.c_int, [C.POINTER(TableLayout), C.c_uint64, C.c_int32, C.c_int32,
+                                      C.POINTER(TableLayout)]),
+    ("pgpu_table_mode", C.c_int, [_P, C.POINTER(TableLayout), _P, _P, C.c_uint64, C.POINTER(C.c_double), C.c_int32,
+                                  C.c_int32, _P, C.c_uint64, _P, C.c_uint64]),
+    ("pgpu_query_collect_mode", C.c_int, [_P, C.c_uint64, C.POINTER(C.c_double), C.c_int32, C.c_int32,
+                                          C.POINTER(C.c_double), C.c_uint64, C.POINTER(TopK), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64), C.c_uint64, C.POINTER(C.c_uint64),
+                                          C.POINTER(QueryStats), C.POINTER(TableLayout)]),
     ("pgpu_query_submit", C.c_int, [_P, C.POINTER(QueryDesc), C.POINTER(_P)]),
     ("pgpu_query_collect", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_uint64,
                                      C.POINTER(C.c_uint64), C.POINTER(QueryStats)]),

@@ -725,7 +725,8 @@ class DistributedExecutor:
 
 def _refuse_distinct(query: QueryContext) -> None:
     """DISTINCTCOUNT across ranks needs the fold after the reduce (pgpu_table_fold on the reduced table), which the
-    multi-GPU combines do not do yet: the server keeps its CPU plan.  PERCENTILE likewise (pgpu_table_select)."""
+    multi-GPU combines do not do yet: the server keeps its CPU plan.  PERCENTILE (pgpu_table_select) and MODE
+    (pgpu_table_mode) likewise."""
     from .distinct import folded_names, has_distinct
     if has_distinct(query):
         raise _lib.UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED, f"{folded_names(query)} is not served by the "

@@ -75,6 +75,11 @@ size_t pgpu_select_temp_bytes(uint64_t N, bool hash, uint64_t inner, int num_cus
 hipError_t pgpu_launch_select(const int64_t* in, uint64_t N, int32_t nsec, bool hash, uint64_t inner,
                               const double* percentiles, int32_t k, const int64_t* folded, int64_t* sel, void* temp,
                               size_t temp_bytes, int num_cus, hipStream_t st);
+// most frequent value over the same axis, behind the fold and the selection (pgpu_mode.hip)
+size_t pgpu_mode_temp_bytes(uint64_t N, bool hash, uint64_t inner, bool avg, int num_cus);
+hipError_t pgpu_launch_mode(const int64_t* in, uint64_t N, int32_t nsec, bool hash, uint64_t inner, const double* values,
+                            uint64_t num_values, bool avg, int64_t* mode, void* temp, size_t temp_bytes, int num_cus,
+                            hipStream_t st);
 
 namespace {
 
@@ -310,8 +315,10 @@ struct Workspace {
   DevMem tk_keys, tk_state;            // pgpu_table_topk: per-row order keys, radix-select state + histogram
   DevMem fold;                         // pgpu_query_collect_fold: the folded table
   DevMem sel_tmp;                      // pgpu_query_collect_select: chunk prefixes / sorted pairs of the selection
+  DevMem mode_tmp, mode_vals;          // pgpu_query_collect_mode: chunk tuples of the mode reduction, the column's values
   PinnedMem h_arena, h_stats, h_total, h_table, h_segcnt, h_leafbits, h_segany, h_fsment;
   PinnedMem h_fold;                    // pgpu_query_collect_fold: a small folded table, compacted on the host
+  PinnedMem h_mode_vals;               // pgpu_query_collect_mode: the caller's values, staged for the copy to mode_vals
   DevMem d_cancel;                     // cancel word (DevParams::cancel): = the query's generation -> stop
   PinnedMem h_cancel;                  // its source for pgpu_query_cancel's copy-engine write
   uint32_t cancel_gen = 0;
@@ -4983,19 +4990,31 @@ int check_percentiles(const double* percentiles, int32_t num_percentiles) {
   return PGPU_OK;
 }
 
-// pgpu_query_collect_fold (num_percentiles = 0) and pgpu_query_collect_select: the fold, the selection behind it on
-// the same stream, then the folded / selected table compacted or trimmed.
+int check_reducers(int32_t reducers, const double* values, uint64_t num_values) {
+  if (reducers == 0 || (reducers & ~(PGPU_MODE_MIN | PGPU_MODE_MAX | PGPU_MODE_AVG)))
+    return fail(PGPU_E_INVALID, "mode reducers 0x%x (a mask of PGPU_MODE_MIN, PGPU_MODE_MAX, PGPU_MODE_AVG)", reducers);
+  if ((reducers & PGPU_MODE_AVG) && (!values || num_values == 0))
+    return fail(PGPU_E_INVALID, "PGPU_MODE_AVG without the column's values");
+  return PGPU_OK;
+}
+
+// pgpu_query_collect_fold (num_percentiles = 0, reducers = 0), pgpu_query_collect_select (reducers = 0) and
+// pgpu_query_collect_mode: the fold, the selection and the mode reduction behind it on the same stream, then the
+// resulting table compacted or trimmed.  reducers < 0: a mode collect whose mask the layout check is to refuse.
 int collect_folded(pgpu_query* qq, uint64_t inner_keys, const double* percentiles, int32_t num_percentiles,
-                   const pgpu_topk* order, int64_t* out_keys, int64_t* out_cells, uint64_t capacity,
-                   uint64_t* out_num_groups, pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
+                   int32_t reducers, const double* values, uint64_t num_values, const pgpu_topk* order,
+                   int64_t* out_keys, int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
+                   pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
   if (!qq || !qq->tws || !out_num_groups) return fail(PGPU_E_INVALID, "query was not submitted");
   // (a cancelled or timed-out query returns here: nothing is folded)
   int rc = pgpu_query_wait(qq, out_stats);
   pgpu_table_layout F;
   if (rc == PGPU_OK)
-    rc = num_percentiles ? pgpu_select_layout_of(&qq->layout, inner_keys, num_percentiles, &F)
-                         : pgpu_fold_layout_of(&qq->layout, inner_keys, &F);
+    rc = reducers ? pgpu_mode_layout_of(&qq->layout, inner_keys, num_percentiles, reducers, &F)
+         : num_percentiles ? pgpu_select_layout_of(&qq->layout, inner_keys, num_percentiles, &F)
+                           : pgpu_fold_layout_of(&qq->layout, inner_keys, &F);
   if (rc == PGPU_OK && num_percentiles) rc = check_percentiles(percentiles, num_percentiles);
+  if (rc == PGPU_OK && reducers) rc = check_reducers(reducers, values, num_values);
   if (rc == PGPU_OK) {
     // the table is complete (waited above): fold and compact it on the query's own workspace stream
     Workspace* ws = qq->ws;
@@ -5015,6 +5034,28 @@ int collect_folded(pgpu_query* qq, uint64_t inner_keys, const double* percentile
                                (int64_t*)ws->fold.p + (uint64_t)(L.num_sections + 1) * inner_keys, ws->sel_tmp.p, tb,
                                qq->ctx->num_cus, ws->stream);
       if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table select: %s", hipGetErrorString(e));
+    }
+    if (rc == PGPU_OK && reducers) {
+      const bool hash = L.key_kind == PGPU_KEYS_HASH;
+      const bool avg = (reducers & PGPU_MODE_AVG) != 0;
+      const size_t tb = pgpu_mode_temp_bytes(L.num_keys, hash, inner_keys, avg, qq->ctx->num_cus);
+      e = ws->mode_tmp.ensure(tb + 16, qq->ctx->mpool, ws->stream);
+      if (e == hipSuccess && avg) {
+        // the caller's values are read here, into pinned memory the copy to the device may outlive this call from
+        const size_t vb = 8 * (size_t)num_values;
+        e = ws->h_mode_vals.ensure(vb);
+        if (e == hipSuccess) e = ws->mode_vals.ensure(vb, qq->ctx->mpool, ws->stream);
+        if (e == hipSuccess) {
+          memcpy(ws->h_mode_vals.p, values, vb);
+          e = hipMemcpyAsync(ws->mode_vals.p, ws->h_mode_vals.p, vb, hipMemcpyHostToDevice, ws->stream);
+        }
+      }
+      if (e == hipSuccess)
+        e = pgpu_launch_mode((const int64_t*)qq->tws->table.p, L.num_keys, L.num_sections, hash, inner_keys,
+                             avg ? (const double*)ws->mode_vals.p : nullptr, avg ? num_values : 0, avg,
+                             (int64_t*)ws->fold.p + (uint64_t)(F.num_sections - (avg ? 5 : 4)) * inner_keys,
+                             ws->mode_tmp.p, tb, qq->ctx->num_cus, ws->stream);
+      if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table mode: %s", hipGetErrorString(e));
     }
   }
   const bool trim = order && order->k > 0 && inner_keys > order->k;
@@ -5061,8 +5102,8 @@ extern "C" {
 int pgpu_query_collect_fold(pgpu_query* qq, uint64_t inner_keys, const pgpu_topk* order, int64_t* out_keys,
                             int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
                             pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
-  return collect_folded(qq, inner_keys, nullptr, 0, order, out_keys, out_cells, capacity, out_num_groups, out_stats,
-                        out_layout);
+  return collect_folded(qq, inner_keys, nullptr, 0, 0, nullptr, 0, order, out_keys, out_cells, capacity, out_num_groups,
+                        out_stats, out_layout);
 }
 
 // ---- PERCENTILE: rank selection behind the fold (include/pinot_gpu.h; kernels in pgpu_select.hip) -------------------
@@ -5134,8 +5175,88 @@ int pgpu_query_collect_select(pgpu_query* qq, uint64_t inner_keys, const double*
     // (never the plain fold by accident: the layout check refuses it after the wait, with the query released)
     num_percentiles = -1;
   }
-  return collect_folded(qq, inner_keys, percentiles, num_percentiles, order, out_keys, out_cells, capacity,
-                        out_num_groups, out_stats, out_layout);
+  return collect_folded(qq, inner_keys, percentiles, num_percentiles, 0, nullptr, 0, order, out_keys, out_cells,
+                        capacity, out_num_groups, out_stats, out_layout);
+}
+
+// ---- MODE: the most frequent value behind the fold (include/pinot_gpu.h; kernels in pgpu_mode.hip) -------------------
+int pgpu_mode_layout_of(const pgpu_table_layout* in, uint64_t inner_keys, int32_t num_percentiles, int32_t reducers,
+                        pgpu_table_layout* out) {
+  if (!in || !out) return fail(PGPU_E_INVALID, "null argument");
+  if (reducers <= 0 || (reducers & ~(PGPU_MODE_MIN | PGPU_MODE_MAX | PGPU_MODE_AVG)))
+    return fail(PGPU_E_INVALID, "mode reducers 0x%x (a mask of PGPU_MODE_MIN, PGPU_MODE_MAX, PGPU_MODE_AVG)", reducers);
+  pgpu_table_layout F;
+  const int rc = num_percentiles ? pgpu_select_layout_of(in, inner_keys, num_percentiles, &F)
+                                 : pgpu_fold_layout_of(in, inner_keys, &F);
+  if (rc) return rc;
+  const bool avg = (reducers & PGPU_MODE_AVG) != 0;
+  const int more = avg ? 5 : 4;
+  if (F.num_sections + more > PGPU_MAX_SECTIONS)
+    return fail(PGPU_E_UNSUPPORTED, "no section left for the %d mode sections (%d in use)", more, F.num_sections);
+  // the distinct count and the percentiles took the first unused aggregation entries: LO and HI take the next two
+  int n = 16;
+  while (n > 0 && F.agg_section[n - 1] == 0 && F.agg_value_type[n - 1] == 0) --n;
+  if (n + 2 > 16) return fail(PGPU_E_UNSUPPORTED, "no aggregation entry left for the mode");
+  for (int j = 0; j < more; ++j) F.section_op[F.num_sections + j] = j == 4 ? PGPU_RED_SUM_F64 : PGPU_RED_SUM_I64;
+  for (int j = 0; j < 2; ++j) {  // M, T, then LO, HI
+    F.agg_section[n + j] = F.num_sections + 2 + j;
+    F.agg_value_type[n + j] = PGPU_LONG;
+    F.agg_sum_parts[n + j] = 1;
+    F.agg_sum_exp[n + j] = 0;
+  }
+  F.num_sections += more;
+  *out = F;
+  return PGPU_OK;
+}
+
+int pgpu_table_mode(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
+                    uint64_t inner_keys, const double* percentiles, int32_t num_percentiles, int32_t reducers,
+                    const double* dev_values, uint64_t num_values, void* dev_out, uint64_t out_bytes) {
+  if (!ctx || !in_layout || !dev_table || !dev_out) return fail(PGPU_E_INVALID, "null argument");
+  pgpu_table_layout F;
+  int rc = pgpu_mode_layout_of(in_layout, inner_keys, num_percentiles, reducers, &F);
+  if (rc == PGPU_OK && num_percentiles) rc = check_percentiles(percentiles, num_percentiles);
+  if (rc == PGPU_OK) rc = check_reducers(reducers, dev_values, num_values);
+  if (rc) return rc;
+  if (out_bytes < pgpu_table_bytes(&F))
+    return fail(PGPU_E_INVALID, "mode table needs %llu bytes, %llu given", (unsigned long long)pgpu_table_bytes(&F),
+                (unsigned long long)out_bytes);
+  if (in_layout->num_keys == 0) return fail(PGPU_E_INVALID, "empty table");
+  // the fold and the selection, as pgpu_table_fold / pgpu_table_select enqueue them
+  if (num_percentiles)
+    rc = pgpu_table_select(ctx, in_layout, dev_table, stream, inner_keys, percentiles, num_percentiles, dev_out,
+                           out_bytes);
+  else
+    rc = pgpu_table_fold(ctx, in_layout, dev_table, stream, inner_keys, dev_out, out_bytes);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const bool hash = in_layout->key_kind == PGPU_KEYS_HASH;
+  const bool avg = (reducers & PGPU_MODE_AVG) != 0;
+  // the temporary memory is taken and given back in stream order: nothing waits for the kernels
+  const size_t tb = pgpu_mode_temp_bytes(in_layout->num_keys, hash, inner_keys, avg, ctx->num_cus);
+  void* temp = nullptr;
+  if (tb) {
+    if (ctx->mpool) HIP_TRY(hipMallocFromPoolAsync(&temp, tb, ctx->mpool, st));
+    else HIP_TRY(hipMallocAsync(&temp, tb, st));
+  }
+  const hipError_t e = pgpu_launch_mode((const int64_t*)dev_table, in_layout->num_keys, in_layout->num_sections, hash,
+                                        inner_keys, avg ? dev_values : nullptr, avg ? num_values : 0, avg,
+                                        (int64_t*)dev_out + (uint64_t)(F.num_sections - (avg ? 5 : 4)) * inner_keys,
+                                        temp, tb, ctx->num_cus, st);
+  if (temp) (void)hipFreeAsync(temp, st);
+  if (e != hipSuccess) return fail(PGPU_E_HIP, "table mode: %s", hipGetErrorString(e));
+  return PGPU_OK;
+}
+
+int pgpu_query_collect_mode(pgpu_query* qq, uint64_t inner_keys, const double* percentiles, int32_t num_percentiles,
+                            int32_t reducers, const double* values, uint64_t num_values, const pgpu_topk* order,
+                            int64_t* out_keys, int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
+                            pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
+  // (never the plain fold or selection by accident: the layout check refuses a bad mask or a negative number of
+  // percentiles after the wait, with the query released)
+  if (reducers == 0) reducers = -1;
+  return collect_folded(qq, inner_keys, percentiles, num_percentiles, reducers, values, num_values, order, out_keys,
+                        out_cells, capacity, out_num_groups, out_stats, out_layout);
 }
 
 }  // extern "C"

@@ -317,6 +317,11 @@ size_t hash_sort_temp(uint64_t N) {
 
 }  // namespace
 
+// The same cut for the mode reduction over the same axis (pgpu_mode.hip).
+void pgpu_select_chunks(uint64_t inner, uint64_t card, int num_cus, uint64_t* chunk, uint32_t* nchunks) {
+  chunks_of(inner, card, num_cus, chunk, nchunks);
+}
+
 // Temporary bytes pgpu_launch_select needs for this input (0: none).
 size_t pgpu_select_temp_bytes(uint64_t N, bool hash, uint64_t inner, int num_cus) {
   if (inner == 0 || N == 0) return 0;

@@ -290,13 +290,13 @@ def _agg_column(a, result_name: bool) -> Tuple[str, str]:
 
 def _refuse_distinct(query: QueryContext) -> None:
     """DISTINCTCOUNT's broker-mergeable intermediate is the value set (DistinctCountAggregationFunction.java:252-310),
-    and PERCENTILE's the value list (PercentileAggregationFunction.java:82-100), which the folded table no longer
-    holds: no DataTable for such a query."""
+    PERCENTILE's the value list (PercentileAggregationFunction.java:82-100) and MODE's the value -> count map
+    (ModeAggregationFunction.java:416-456), which the folded table no longer holds: no DataTable for such a query."""
     from .distinct import folded_names, has_distinct
     if has_distinct(query):
         from ._lib import PGPU_E_UNSUPPORTED, UnsupportedPlanError
         raise UnsupportedPlanError(PGPU_E_UNSUPPORTED, f"no DataTable for a {folded_names(query)} query: its "
-                                                       "intermediate result is the value set or list")
+                                                       "intermediate result is the value set, list or count map")
 
 
 def server_data_table(query: QueryContext, result, group_types: Sequence[int] = ()) -> DataTable:

@@ -20,6 +20,12 @@ Exact PERCENTILE (PercentileAggregationFunction.java:82-100,152-165: every value
 the counts of ``Q'`` along ``cid`` are that sorted multiset, and the device picks the smallest ``cid`` whose running
 count passes the rank behind the fold (pgpu_query_collect_select).  One pass per column carries DISTINCTCOUNT(c) and
 every percentile of ``c`` together -- one table, one fold, K picks; the final value is ``float(dictionary[cid])``.
+
+Exact MODE (ModeAggregationFunction.java:463-672: a value -> count map per group, the value of the largest count, and
+of several such values the smallest, the largest or their mean, :59-75) rides them too: the counts of ``Q'`` along
+``cid`` are that map, and one reduction behind the fold (pgpu_query_collect_mode) leaves per group the largest count,
+the number of tied ids, the smallest and the largest of them and -- for the AVG reducer -- the sum of their values.  The
+pass of ``c`` carries every MODE of ``c`` whatever its reducer: one table, one fold, one mode reduction.
 """
 from __future__ import annotations
 
@@ -31,12 +37,14 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 from . import _lib
 from ._lib import UnsupportedPlanError
-from .query import MV_AGGS, AggregationSpec, OrderByExpr, QueryContext
+from .query import MODE_REDUCERS, MV_AGGS, AggregationSpec, OrderByExpr, QueryContext
 
 UNLIMITED = 1 << 62
 DISTINCT = "DISTINCTCOUNT"
 PERCENTILE = "PERCENTILE"
-FOLDED = (DISTINCT, PERCENTILE)  # the functions answered from the table folded over their column
+MODE = "MODE"
+FOLDED = (DISTINCT, PERCENTILE, MODE)  # the functions answered from the table folded over their column
+MODE_BITS = {"MIN": _lib.PGPU_MODE_MIN, "MAX": _lib.PGPU_MODE_MAX, "AVG": _lib.PGPU_MODE_AVG}
 
 
 def has_distinct(query: QueryContext) -> bool:
@@ -44,7 +52,8 @@ def has_distinct(query: QueryContext) -> bool:
 
 
 def folded_names(query: QueryContext) -> str:
-    """The folded functions a query holds, for messages: 'DISTINCTCOUNT', 'PERCENTILE' or 'DISTINCTCOUNT / PERCENTILE'."""
+    """The folded functions a query holds, for messages: 'DISTINCTCOUNT', 'PERCENTILE', 'MODE' or several of them as
+    'DISTINCTCOUNT / PERCENTILE'."""
     return " / ".join(f for f in FOLDED if any(a.function == f for a in query.aggregations))
 
 
@@ -54,14 +63,27 @@ def _unsupported(why: str) -> UnsupportedPlanError:
 
 @dataclass
 class DistinctPass:
-    """One pass of a DISTINCTCOUNT / PERCENTILE query."""
+    """One pass of a DISTINCTCOUNT / PERCENTILE / MODE query."""
     query: QueryContext     # Q': GROUP BY g..., column with the pass's plain aggregations
     folded: QueryContext    # what the folded table answers: GROUP BY g... with Q's aggregations + DISTINCTCOUNT(column)
-                            # + the pass's percentiles (their cells hold the selected ids of column)
+                            # + the pass's percentiles (their cells hold the selected ids of column) + when the pass
+                            # has a MODE: MODE(column, 'MIN'), MODE(column, 'MAX') (the cells LO and HI: ids of
+                            # column) and, when asked for, MODE(column, 'AVG') (S / T: already the value)
     column: str             # the folded column
     plain: List[int]        # original indexes of Q's aggregations, in their order ([]: Q' carries an inserted COUNT(*))
     distinct: List[int]     # original indexes of DISTINCTCOUNT(column) (every mention of it)
     percentile: List[int] = field(default_factory=list)  # original indexes of PERCENTILE(column, p), one pick each
+
+    mode: List[int] = field(default_factory=list)  # original indexes of MODE(column, reducer), every reducer
+
+    @property
+    def reducers(self) -> int:
+        """The reducer mask of the pass's mode reduction (PGPU_MODE_*), 0 without a MODE."""
+        mask = 0
+        for a in self.folded.aggregations:
+            if a.function == MODE:
+                mask |= MODE_BITS[a.reducer]
+        return mask
 
     @property
     def percentiles(self) -> List[float]:
@@ -70,24 +92,24 @@ class DistinctPass:
 
 
 def lower(query: QueryContext) -> List[DistinctPass]:
-    """The passes of a DISTINCTCOUNT / PERCENTILE query.  Raises UnsupportedPlanError for the combinations not
+    """The passes of a DISTINCTCOUNT / PERCENTILE / MODE query.  Raises UnsupportedPlanError for the combinations not
     served."""
     if not has_distinct(query):
-        raise ValueError("query has no DISTINCTCOUNT or PERCENTILE")
+        raise ValueError("query has no DISTINCTCOUNT, PERCENTILE or MODE")
     what = folded_names(query)
     if query.has_filtered_aggregations:
         raise _unsupported(f"{what} in a query with FILTER(WHERE ...) aggregations")
     if any(a.function in MV_AGGS for a in query.aggregations):
         raise _unsupported(f"{what} together with *MV aggregations")
     plain = [i for i, a in enumerate(query.aggregations) if a.function not in FOLDED]
-    by_col: Dict[str, Tuple[List[int], List[int]]] = {}
+    by_col: Dict[str, Tuple[List[int], List[int], List[int]]] = {}
     for i, a in enumerate(query.aggregations):
         if a.function in FOLDED:
             if a.column in query.group_by:
                 raise _unsupported(f"{a.function} of the group column {a.column!r}")
-            by_col.setdefault(a.column, ([], []))[a.function == PERCENTILE].append(i)
+            by_col.setdefault(a.column, ([], [], []))[FOLDED.index(a.function)].append(i)
     passes = []
-    for k, (col, (idx, pidx)) in enumerate(by_col.items()):
+    for k, (col, (idx, pidx, midx)) in enumerate(by_col.items()):
         if len(pidx) > _lib.PGPU_SELECT_MAX:
             raise _unsupported(f"{len(pidx)} percentiles of {col!r} (at most {_lib.PGPU_SELECT_MAX} per column)")
         mine = plain if k == 0 else []
@@ -97,22 +119,35 @@ def lower(query: QueryContext) -> List[DistinctPass]:
                            filter=query.filter, group_by=groups + [col], order_by=[], limit=UNLIMITED,
                            options=dict(query.options))
         faggs = list(aggs) + [AggregationSpec(DISTINCT, col)] + [query.aggregations[i] for i in pidx]
+        if midx:  # LO and HI are always there; S only when the AVG reducer is asked for
+            faggs += [AggregationSpec(MODE, col, reducer=r) for r in ("MIN", "MAX")]
+            if any(query.aggregations[i].reducer == "AVG" for i in midx):
+                faggs.append(AggregationSpec(MODE, col, reducer="AVG"))
         folded = QueryContext(table=query.table, select=groups + faggs, aggregations=faggs, filter=query.filter,
                               group_by=groups, order_by=[], limit=UNLIMITED, options=dict(query.options))
-        passes.append(DistinctPass(low, folded, col, list(mine), idx, pidx))
+        passes.append(DistinctPass(low, folded, col, list(mine), idx, pidx, midx))
     return passes
 
 
 def order_pass(query: QueryContext, passes: Sequence[DistinctPass]) -> Optional[Tuple[int, OrderByExpr]]:
     """(pass, expression) the server's ORDER BY trim selects by: the first ORDER BY expression, in the pass whose folded
-    table holds it -- a group column or a plain aggregation in the first pass, DISTINCTCOUNT(c) or a percentile of c in
-    c's pass (its cell is the selected id of c: the order of the ids is the order of the values).  The other passes
-    return every group; the join keeps the groups every pass returned."""
+    table holds it -- a group column or a plain aggregation in the first pass, DISTINCTCOUNT(c), a percentile of c or a
+    MIN / MAX-reducer MODE of c in c's pass (its cell is an id of c: the order of the ids is the order of the values).
+    A MODE is matched by function, column and reducer -- mode(c) names every reducer of c; the mean of several modes
+    is no cell of the table to order by.  The other passes return every group; the join keeps the groups every pass
+    returned."""
     if not query.group_by or not query.order_by:
         return None
     ob = query.order_by[0]
+    if ob.aggregation is not None and ob.aggregation.function == MODE:
+        if ob.aggregation.reducer == "AVG":
+            raise _unsupported(f"ORDER BY MODE({ob.aggregation.column}, 'AVG'): the trim on the device orders by a "
+                               "mode's dictionary id, which the mean of several modes does not have")
+        for pi, p in enumerate(passes):
+            if ob.aggregation in p.folded.aggregations:
+                return pi, ob
     for pi, p in enumerate(passes):
-        if any(ob.expression == a.result_name for a in p.folded.aggregations if a.function in FOLDED):
+        if any(ob.expression == a.result_name for a in p.folded.aggregations if a.function in (DISTINCT, PERCENTILE)):
             return pi, ob
     return 0, ob
 
@@ -132,22 +167,33 @@ def _join_stats(query: QueryContext, results: Sequence):
 
 def raise_result(query: QueryContext, passes: Sequence[DistinctPass], results: Sequence):
     """The original query's QueryResult from the passes' folded results (QueryResults of ``DistinctPass.folded``; a pass
-    with percentiles carries the global dictionary of its column as ``value_dictionary``)."""
+    with percentiles or modes carries the global dictionary of its column as ``value_dictionary``)."""
     from .plan import QueryResult, order_and_limit, to_select_order
 
     res = QueryResult(query=query, stats=_join_stats(query, results))
     na = len(query.aggregations)
-    dicts = {id(p): r.value_dictionary for p, r in zip(passes, results) if p.percentile}
+    dicts = {id(p): r.value_dictionary for p, r in zip(passes, results) if p.percentile or p.mode}
 
     def place(fin: list, p: DistinctPass, vals: Sequence) -> None:
         for j, i in enumerate(p.plain):
             fin[i] = vals[j]
-        nd = len(vals) - 1 - len(p.percentile)  # plain aggregations, then the distinct count, then the picks
+        nm = sum(a.function == MODE for a in p.folded.aggregations)
+        nd = len(vals) - 1 - len(p.percentile) - nm  # plain aggregations, the distinct count, the picks, the modes
         for i in p.distinct:
             fin[i] = int(vals[nd])  # ColumnDataType.INT (DistinctCountAggregationFunction.java:303-310)
         for j, i in enumerate(p.percentile):
             # DOUBLE; no value met: DEFAULT_FINAL_RESULT (PercentileAggregationFunction.java:152-165)
             fin[i] = float(dicts[id(p)][int(vals[nd + 1 + j])]) if int(vals[nd]) > 0 else -math.inf
+        for i in p.mode:
+            # DOUBLE.  MIN / MAX: the value of the smallest / largest tied id, converted once; AVG: S / T, taken where
+            # the cells are decoded (plan.mode_value).  No value met (M = 0, as the distinct count):
+            # DEFAULT_FINAL_RESULT (ModeAggregationFunction.java:61,468-470)
+            r = query.aggregations[i].reducer
+            v = vals[len(vals) - nm + MODE_REDUCERS.index(r)]
+            if int(vals[nd]) <= 0:
+                fin[i] = -math.inf
+            else:
+                fin[i] = float(v) if r == "AVG" else float(dicts[id(p)][int(v)])
 
     if not query.group_by:
         fin: list = [None] * na

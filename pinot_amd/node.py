@@ -156,8 +156,8 @@ class GpuNode:
 
 def _refuse_distinct(query: QueryContext) -> None:
     """DISTINCTCOUNT on a node needs the fold after the devices' tables are merged (pgpu_table_fold on the merged
-    table), which pgpu_node_collect does not do yet: the server keeps its CPU plan.  PERCENTILE likewise
-    (pgpu_table_select)."""
+    table), which pgpu_node_collect does not do yet: the server keeps its CPU plan.  PERCENTILE (pgpu_table_select)
+    and MODE (pgpu_table_mode) likewise."""
     from .distinct import folded_names, has_distinct
     if has_distinct(query):
         raise _lib.UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED,

@@ -41,7 +41,8 @@ from ._lib import (ExprNode, Literal, PGPU_AGG_AVG, PGPU_AGG_COUNT, PGPU_AGG_MAX
                    UnsupportedPlanError)
 from .predicate import (DictPredicateEvaluator, RawPredicateEvaluator, SortedDictionary, get_predicate_evaluator,
                         get_raw_predicate_evaluator)
-from .query import MV_AGGS, UNBOUNDED, AggregationSpec, FilterContext, QueryContext, split_filtered_aggregations
+from .query import (MV_AGGS, UNBOUNDED, AggregationSpec, FilterContext, QueryContext, row_index,
+                    split_filtered_aggregations)
 from .distinct import FOLDED, folded_names, has_distinct
 from .segment import DOCID_COLUMN, GpuContext, GpuSegment
 
@@ -331,7 +332,7 @@ class QueryResult:
         self._columns: Optional["GroupColumns"] = None
         self._group_rows: Optional[List[tuple]] = None
         self._intermediate: Optional[dict] = None
-        self.value_dictionary = None  # a folded pass with percentiles: the global dictionary of the folded column
+        self.value_dictionary = None  # a folded pass: the global dictionary of the folded column
 
     @property
     def group_rows(self) -> Optional[List[tuple]]:
@@ -410,6 +411,20 @@ def final_value(fn: str, cell_count: int, cell: Optional[int], op: int, vtype: i
     raise ValueError(fn)
 
 
+def mode_value(a: AggregationSpec, aggs: Sequence[AggregationSpec], L, cells: np.ndarray) -> np.ndarray:
+    """MODE aggregation `a` of a folded query over rows of cells ([rows, sections]) of its mode table.  The appended
+    sections M, T, LO, HI (, S) are the layout's last (pgpu_mode_layout_of; S when the query holds an AVG reducer):
+    MIN -> LO and MAX -> HI, ids of the folded column as int64 (distinct.raise_result turns them into values);
+    AVG -> S / T as float64, -inf where nothing is tied (T = 0: the key met no value)."""
+    avg = any(x.function == "MODE" and x.reducer == "AVG" for x in aggs)
+    base = L.num_sections - (5 if avg else 4)
+    if a.reducer != "AVG":
+        return cells[:, base + (2 if a.reducer == "MIN" else 3)].astype(np.int64)
+    t = cells[:, base + 1]
+    s = np.ascontiguousarray(cells[:, base + 4]).view(np.float64)
+    return np.where(t > 0, s / np.maximum(t, 1), -np.inf)
+
+
 def intermediate_value(fn: str, cell_count: int, cell, op: int, vtype: int):
     if fn == "AVG":
         s = float(cell) if op == PGPU_RED_SUM_I64 else float(np.int64(cell).view(np.float64))
@@ -419,10 +434,9 @@ def intermediate_value(fn: str, cell_count: int, cell, op: int, vtype: int):
 
 def order_and_limit(query: QueryContext, rows: List[tuple]) -> List[tuple]:
     """Broker-side ORDER BY / LIMIT over final rows (GroupByDataTableReducer, IndexedTable.finish)."""
-    names = list(query.group_by) + [a.result_name for a in query.aggregations]
     if query.order_by:
         for ob in reversed(query.order_by):
-            idx = names.index(ob.expression)
+            idx = row_index(query, ob)
             rows = sorted(rows, key=lambda r, i=idx: r[i], reverse=not ob.ascending)
     return rows[: query.limit]
 
@@ -442,8 +456,7 @@ def topk_spec(query: QueryContext, cards: Sequence[int], k: int, key_base: int =
     if not query.group_by or not query.order_by or k <= 0:
         return None
     ob = query.order_by[0]
-    names = list(query.group_by) + [a.result_name for a in query.aggregations]
-    i = names.index(ob.expression)
+    i = row_index(query, ob)
     ng = len(query.group_by)
     t = _lib.TopK()
     t.k, t.key_base, t.descending = int(k), int(key_base), 0 if ob.ascending else 1
@@ -455,18 +468,14 @@ def topk_spec(query: QueryContext, cards: Sequence[int], k: int, key_base: int =
     else:
         t.source, t.agg_index = _lib.PGPU_TOPK_AGG, i - ng
         fn = query.aggregations[i - ng].function
-        # (a folded table's distinct count and selected ids are LONG SUM sections: pgpu_select_layout_of)
+        # (a folded table's distinct count, selected ids and smallest / largest modes are LONG SUM sections:
+        # pgpu_select_layout_of, pgpu_mode_layout_of)
         t.agg_fn = PGPU_AGG_SUM if fn in FOLDED else AGG_FN[fn]
     return t
 
 
 def to_select_order(query: QueryContext, row: tuple) -> tuple:
-    names = list(query.group_by) + [a.result_name for a in query.aggregations]
-    out = []
-    for s in query.select:
-        key = s if isinstance(s, str) else s.result_name
-        out.append(row[names.index(key)])
-    return tuple(out)
+    return tuple(row[row_index(query, s)] for s in query.select)
 
 
 def order_key(v: np.ndarray) -> np.ndarray:
@@ -884,9 +893,10 @@ class GpuPlanMaker:
             if segments and segments[0].column(p.column).is_mv:
                 raise UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED,
                                            f"{what} over the multi-value column {p.column!r}")
-            if p.percentile and any(s.column(p.column).data_type == _lib.PGPU_STRING for s in segments):
+            if (p.percentile or p.mode) and any(s.column(p.column).data_type == _lib.PGPU_STRING for s in segments):
                 raise UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED,
-                                           f"PERCENTILE over the STRING column {p.column!r}")
+                                           f"{'PERCENTILE' if p.percentile else 'MODE'} over the STRING column "
+                                           f"{p.column!r}")
         if query.group_by and self.num_groups_limit > 0:
             for s in segments:
                 space = 1
@@ -920,6 +930,7 @@ class GpuPlanMaker:
             pq = self._launch(prep, segments)
             pq.fold = (inner, F, p.folded)
             pq.percentiles = p.percentiles
+            pq.reducers = p.reducers
             pq.order = order
             pending.append(pq)
         return DistinctPending(self, query, passes, pending)
@@ -936,7 +947,10 @@ class GpuPlanMaker:
             for g in globals_[:-1]:
                 inner *= len(g[0])
             F = TableLayout()
-            if p.percentile:  # the folded table plus one section of selected ids per percentile
+            if p.mode:  # ... plus the mode sections behind them
+                _lib.check(self.ctx._lib.pgpu_mode_layout_of(C.byref(L), inner, len(p.percentile), p.reducers,
+                                                             C.byref(F)))
+            elif p.percentile:  # the folded table plus one section of selected ids per percentile
                 _lib.check(self.ctx._lib.pgpu_select_layout_of(C.byref(L), inner, len(p.percentile), C.byref(F)))
             else:
                 _lib.check(self.ctx._lib.pgpu_fold_layout_of(C.byref(L), inner, C.byref(F)))
@@ -1008,7 +1022,20 @@ class GpuPlanMaker:
         h, pending.handle = pending.handle, None
         query = pending.query
         order = pending.order
-        if fold is not None and pending.percentiles:  # ... and its percentiles picked behind the fold
+        if fold is not None and pending.reducers:  # ... with its percentiles picked and its modes reduced behind the fold
+            query = fold[2]
+            ps = (C.c_double * max(len(pending.percentiles), 1))(*pending.percentiles)
+            vals, nv = None, 0
+            if pending.reducers & _lib.PGPU_MODE_AVG:
+                # each value converted to double once, before any add (ModeAggregationFunction.java:558-572)
+                dv = np.ascontiguousarray(pending.globals_[-1][0], dtype=np.float64)
+                vals, nv = dv.ctypes.data_as(C.POINTER(C.c_double)), len(dv)
+            _lib.check(self.ctx._lib.pgpu_query_collect_mode(h, fold[0], ps, len(pending.percentiles), pending.reducers,
+                                                             vals, nv, C.byref(order) if order is not None else None,
+                                                             keys.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                             cells.ctypes.data_as(C.POINTER(C.c_int64)), cap,
+                                                             C.byref(n), C.byref(st), None))
+        elif fold is not None and pending.percentiles:  # ... and its percentiles picked behind the fold
             query = fold[2]
             ps = (C.c_double * len(pending.percentiles))(*pending.percentiles)
             _lib.check(self.ctx._lib.pgpu_query_collect_select(h, fold[0], ps, len(ps),
@@ -1165,6 +1192,7 @@ class PendingQuery:
     order: Optional[object] = None  # the pgpu_topk given at submit (collect passes the same one)
     fold: Optional[tuple] = None  # a folded (DISTINCTCOUNT / PERCENTILE) pass: (inner keys, folded layout, folded query)
     percentiles: Optional[list] = None  # ... and the percentiles picked behind its fold (pgpu_query_collect_select)
+    reducers: int = 0  # ... and the reducer mask of the mode reduction behind them (pgpu_query_collect_mode)
 
     def cancel(self) -> None:
         """Stop the query (pgpu_query_cancel): its kernels skip their remaining tiles and collect raises
@@ -1227,6 +1255,12 @@ def finish(query: QueryContext, table: GroupTable, global_dicts: Sequence, stats
         cnt = int(row_cells[0])
         fin, inter = [], []
         for ai, a in enumerate(aggs):
+            if a.function == "MODE":  # the mode sections of a folded table, not an aggregation entry's cell
+                v = mode_value(a, aggs, L, np.asarray(row_cells, dtype=np.int64).reshape(1, -1))[0]
+                v = float(v) if a.reducer == "AVG" else int(v)
+                fin.append(v)
+                inter.append(v)
+                continue
             sec = L.agg_section[ai]
             cell = join_parts(row_cells, sec, L.agg_sum_parts[ai], sum_exp_of(L, ai)) if sec > 0 else None
             op = L.section_op[sec]
@@ -1386,6 +1420,8 @@ class GroupColumns:
         s = None
         if fn == "COUNT":
             f = cnt.astype(np.int64)
+        elif fn == "MODE":
+            f = mode_value(a, self.query.aggregations, L, cells)
         elif fn in FOLDED:
             f = cell.astype(np.int64)
         elif fn in ("SUM", "AVG") and L.agg_sum_parts[ai] > 1:
@@ -1409,10 +1445,9 @@ class GroupColumns:
     def finals(self) -> List[np.ndarray]:
         return [self.final(ai)[0] for ai in range(len(self.query.aggregations))]
 
-    def _column(self, name: str, idx: Optional[np.ndarray] = None) -> np.ndarray:
+    def _column(self, ob, idx: Optional[np.ndarray] = None) -> np.ndarray:
         ng = len(self.query.group_by)
-        names = list(self.query.group_by) + [a.result_name for a in self.query.aggregations]
-        i = names.index(name)
+        i = row_index(self.query, ob)
         return self.value(i, idx) if i < ng else self.final(i - ng, idx)[0]
 
     def order_and_limit(self, limit: Optional[int] = None) -> np.ndarray:
@@ -1426,7 +1461,7 @@ class GroupColumns:
             return np.arange(min(n, lim))
 
         def key_of(ob, idx=None):
-            c = self._column(ob.expression, idx)
+            c = self._column(ob, idx)
             if c.dtype.kind in "iuf":
                 kk = c.astype(np.float64) if c.dtype.kind == "f" else c.astype(np.int64)
             else:
@@ -1447,7 +1482,7 @@ class GroupColumns:
         parts = [self.value(gi, idx).tolist() for gi in range(len(self.global_dicts))]
         for ai, a in enumerate(self.query.aggregations):
             f = self.final(ai, idx)[0]
-            parts.append([int(x) for x in f.tolist()] if a.function in ("COUNT",) + FOLDED
+            parts.append([int(x) for x in f.tolist()] if a.function in ("COUNT",) + FOLDED and a.reducer != "AVG"
                          else f.tolist())
         return [tuple(r) for r in zip(*parts)] if parts else []
 

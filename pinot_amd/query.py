@@ -46,15 +46,18 @@ class FilterContext:
 
 @dataclass(frozen=True)
 class AggregationSpec:
-    function: str        # COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT, PERCENTILE; COUNTMV, SUMMV, MINMV, MAXMV, AVGMV
+    function: str        # COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT, PERCENTILE, MODE; COUNTMV, SUMMV, MINMV, MAXMV, AVGMV
                          # (multi-value columns)
     column: Optional[str]  # None for COUNT(*)
     filter_key: Optional[str] = None  # FILTER(WHERE ...) clause text; its FilterContext is QueryContext.agg_filters
     percentile: Optional[float] = None  # PERCENTILE only: 0..100
     percentile_arg: bool = False        # written PERCENTILE(col, p), not PERCENTILE<N>(col): the result's name differs
+    reducer: Optional[str] = None       # MODE only: MIN, MAX or AVG over several modes (MultiModeReducerType)
 
     @property
     def result_name(self) -> str:
+        # (MODE: mode(col) whatever the reducer, BaseSingleInputAggregationFunction.getResultColumnName -- two reducers
+        # of one column share their name, which is why rows are indexed through row_index below)
         if self.function == "PERCENTILE":  # PercentileAggregationFunction.java:65-70
             if self.percentile_arg:
                 return f"percentile({self.column}, {java_double_string(self.percentile)})"
@@ -79,6 +82,8 @@ def java_double_string(x: float) -> str:
 class OrderByExpr:
     expression: str      # column name or aggregation result name
     ascending: bool = True
+    # a MODE expression only: the aggregation itself, since mode(col) names every reducer of col (not compared)
+    aggregation: Optional[AggregationSpec] = field(default=None, compare=False, repr=False)
 
 
 @dataclass
@@ -134,11 +139,23 @@ class QueryContext:
         return out
 
 
+def row_index(query: QueryContext, item) -> int:
+    """Position of a SELECT item (column name or AggregationSpec) or an OrderByExpr in a row of the query's group
+    columns followed by its aggregations.  By result name, except a MODE: mode(col) is the name of every reducer of
+    col, so it is found by function, column and reducer."""
+    spec = item.aggregation if isinstance(item, OrderByExpr) else item
+    if isinstance(spec, AggregationSpec) and spec.function == "MODE":
+        return len(query.group_by) + query.aggregations.index(spec)
+    name = item.expression if isinstance(item, OrderByExpr) else (item if isinstance(item, str) else item.result_name)
+    return (list(query.group_by) + [a.result_name for a in query.aggregations]).index(name)
+
+
 # ---- SQL front end -------------------------------------------------------------------------------------------
 _TOKEN = re.compile(r"\s*(?:(?P<num>-?\d+(?:\.\d+)?(?:[eE][-+]?\d+)?)|(?P<str>'(?:[^']|'')*')|"
                     r"(?P<op><>|!=|<=|>=|=|<|>|\(|\)|,|\*)|(?P<id>[A-Za-z_][A-Za-z0-9_.$]*))")
 _AGGS = {"COUNT", "SUM", "MIN", "MAX", "AVG", "DISTINCTCOUNT", "COUNTMV", "SUMMV", "MINMV", "MAXMV", "AVGMV"}
 _PERCENTILE = re.compile(r"^PERCENTILE(EST|TDIGEST|RAWEST|RAWTDIGEST|RAW)?(\d*)(MV)?$", re.IGNORECASE)
+MODE_REDUCERS = ("MIN", "MAX", "AVG")  # MultiModeReducerType
 MV_AGGS = {"COUNTMV": "COUNT", "SUMMV": "SUM", "MINMV": "MIN", "MAXMV": "MAX", "AVGMV": "AVG"}
 
 
@@ -214,6 +231,8 @@ class _Parser:
         pm = _PERCENTILE.match(t[1]) if t[0] == "id" and t2 == ("op", "(") else None
         if pm:
             return self.percentile_item(t[1].upper(), pm)
+        if t[0] == "id" and t[1].upper() in ("MODE", "MODEMV") and t2 == ("op", "("):
+            return self.mode_item(t[1].upper())
         if t[0] == "id" and t[1].upper() in _AGGS and t2 == ("op", "("):
             fn = t[1].upper()
             self.i += 2
@@ -271,6 +290,28 @@ class _Parser:
             raise SqlError("PERCENTILE with FILTER(WHERE ...) is not supported")
         return AggregationSpec("PERCENTILE", col, None, p, arg)
 
+    def mode_item(self, name: str) -> AggregationSpec:
+        """MODE(col) or MODE(col, 'MIN' | 'MAX' | 'AVG'): the reducer a quoted literal matched exactly, as
+        MultiModeReducerType.valueOf does, MIN when absent (ModeAggregationFunction.java:59-75)."""
+        if name == "MODEMV":
+            raise SqlError("MODEMV is not supported (MODE over single-value columns only)")
+        self.i += 2
+        col = self.ident()
+        reducer = "MIN"
+        if self.op(","):
+            t = self.peek()
+            if t[0] != "str" or t[1] not in MODE_REDUCERS:
+                raise SqlError(f"MODE: the reducer is one of the quoted literals 'MIN', 'MAX', 'AVG', not {t[1]}")
+            self.i += 1
+            reducer = t[1]
+            if self.peek() == ("op", ","):
+                raise SqlError("MODE takes a column and at most one reducer")
+        self.expect_op(")")
+        nxt = self.peek()
+        if nxt[0] == "id" and nxt[1].upper() == "FILTER":
+            raise SqlError("MODE with FILTER(WHERE ...) is not supported")
+        return AggregationSpec("MODE", col, reducer=reducer)
+
     def order_item(self) -> OrderByExpr:
         item = self.select_item()
         name = item.result_name if isinstance(item, AggregationSpec) else item
@@ -279,6 +320,8 @@ class _Parser:
             asc = False
         else:
             self.kw("ASC")
+        if isinstance(item, AggregationSpec) and item.function == "MODE":
+            return OrderByExpr(name, asc, item)
         return OrderByExpr(name, asc)
 
     def bool_expr(self) -> FilterContext:
