@@ -320,6 +320,33 @@ def check(rc: int) -> None:
         raise PinotGpuError(rc, msg)
 
 
+def folded_layout_of(layout: TableLayout, inner_keys: int, num_percentiles: int, reducers: int) -> TableLayout:
+    """The layout of `layout`'s table folded into `inner_keys` keys, with `num_percentiles` selected ids and the mode
+    sections of the mask `reducers` behind the distinct count: the layout function of the last step asked for."""
+    lib, F = load(), TableLayout()
+    if reducers:
+        check(lib.pgpu_mode_layout_of(C.byref(layout), inner_keys, num_percentiles, reducers, C.byref(F)))
+    elif num_percentiles:
+        check(lib.pgpu_select_layout_of(C.byref(layout), inner_keys, num_percentiles, C.byref(F)))
+    else:
+        check(lib.pgpu_fold_layout_of(C.byref(layout), inner_keys, C.byref(F)))
+    return F
+
+
+def collect_folded(handle, inner_keys: int, percentiles, reducers: int, values, *tail) -> None:
+    """The collect of the same step (pgpu_query_collect_fold / _select / _mode).  percentiles: a list; values: a float64
+    array (read when `reducers` holds PGPU_MODE_AVG) or None; tail: the arguments the three share, from `order` on."""
+    lib = load()
+    ps = (C.c_double * len(percentiles))(*percentiles) if percentiles else None
+    if reducers:
+        vals, nv = (values.ctypes.data_as(C.POINTER(C.c_double)), len(values)) if values is not None else (None, 0)
+        check(lib.pgpu_query_collect_mode(handle, inner_keys, ps, len(percentiles), reducers, vals, nv, *tail))
+    elif percentiles:
+        check(lib.pgpu_query_collect_select(handle, inner_keys, ps, len(percentiles), *tail))
+    else:
+        check(lib.pgpu_query_collect_fold(handle, inner_keys, *tail))
+
+
 def table_bytes(layout: TableLayout) -> int:
     return int(load().pgpu_table_bytes(C.byref(layout)))
 

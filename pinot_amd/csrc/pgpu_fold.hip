@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "../../include/pinot_gpu.h"
+#include "pgpu_axis.h"
 
 // LDS table of fold_cells_kernel: 64 KiB is what a workgroup gets without opting in to more, and two such
 // workgroups still share a CU's 160 KiB, so one's flush overlaps the other's reads.  inner x (nsec + 1) x 8 B
@@ -56,11 +57,7 @@ FI void fold_atomic(int64_t* cell, int32_t op, int64_t v) {
 // Butterfly over the wave's 64 lanes: every lane ends with the combination of all.
 FI int64_t fold_wave(int32_t op, int64_t v) {
 #pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const int lo = __shfl_xor((int)(uint32_t)v, d, 64);
-    const int hi = __shfl_xor((int)(uint32_t)((uint64_t)v >> 32), d, 64);
-    v = fold_combine(op, v, (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
-  }
+  for (int d = 32; d > 0; d >>= 1) v = fold_combine(op, v, shfl_xor64(v, d));
   return v;
 }
 

@@ -9,7 +9,7 @@
 // (ids are ordered as their values).  The tuple of a range of cid is a monoid: of two ranges the larger M wins whole,
 // equal M > 0 merge (T and S add, LO min, HI max).  Counts are compared as int64.
 //
-// Dense input, chunks of cid with the selection's geometry (pgpu_select_chunks) and its two orientations:
+// Dense input, chunks of cid cut as for the selection (chunks_of, pgpu_axis.h) and in its two orientations:
 //   mode_partial_kernel  one tuple per (chunk, g).  inner >= 64 puts lanes along g: a thread walks its chunk in
 //                        ascending cid, eight counts loaded before the first is used.  inner < 64 gives a wave a
 //                        (g, chunk) with its lanes along cid: a lane walks every 64th cid in ascending order, then the
@@ -31,21 +31,18 @@
 #include <algorithm>
 
 #include "../../include/pinot_gpu.h"
+#include "pgpu_axis.h"
 
-#define PGPU_MODE_THREADS 256
-#define PGPU_MODE_WAVES (PGPU_MODE_THREADS / 64)
+#define PGPU_MODE_THREADS PGPU_AXIS_THREADS
+#define PGPU_MODE_WAVES PGPU_AXIS_WAVES
 #define PGPU_MODE_UNROLL 8              // cells per thread whose counts are loaded before any is used
 #define PGPU_MODE_COMBINE_BY_WAVE 4096  // inner below this: the chunks of a key are merged by a wave, not a thread
 
-// Chunks of cid for dense input, as the selection cuts them (pgpu_select.hip).
-void pgpu_select_chunks(uint64_t inner, uint64_t card, int num_cus, uint64_t* chunk, uint32_t* nchunks);
-
-// The tuple sections of `count` keys each: the output ([inner]) or the chunk tuples.  Tuple (chunk, g) is at
-// chunk * sc + g * sg: [chunk][g] (sc = inner, sg = 1) or [g][chunk] (sc = 1, sg = nchunks).
+// The tuple sections of `count` keys each: the output ([inner]) or the chunk tuples, laid out by `at`.
 struct ModeAt {
   int64_t *m, *t, *lo, *hi;
   double* s;
-  uint64_t sc, sg;
+  PartialAt at;
 };
 
 namespace {
@@ -88,11 +85,6 @@ FI void mode_cell(ModeTuple& a, int64_t cnt, uint64_t cid, const double* __restr
   a.hi = (int64_t)cid;
 }
 
-FI int64_t shfl_xor64(int64_t v, int d) {
-  const int lo = __shfl_xor((int)(uint32_t)v, d, 64);
-  const int hi = __shfl_xor((int)(uint32_t)((uint64_t)v >> 32), d, 64);
-  return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-}
 // Butterfly over the wave's 64 lanes: every lane ends with the merge of all, in the same fixed tree.
 template <bool AVG>
 FI ModeTuple mode_wave(ModeTuple a) {
@@ -128,7 +120,7 @@ FI void mode_store(const ModeAt& at, uint64_t i, const ModeTuple& a) {
   if (AVG) at.s[i] = a.s;
 }
 
-// dst = the chunk tuples, or with one chunk the output itself (sc = 0, sg = 1).
+// dst = the chunk tuples, or with one chunk the output itself (at = {0, 1}).
 template <bool WAVE, bool AVG>
 __global__ __launch_bounds__(PGPU_MODE_THREADS) void mode_partial_kernel(const int64_t* __restrict__ in, uint64_t inner,
                                                                          uint64_t card, uint64_t chunk, uint32_t nchunks,
@@ -163,7 +155,7 @@ __global__ __launch_bounds__(PGPU_MODE_THREADS) void mode_partial_kernel(const i
     a = mode_wave<AVG>(a);
     if (lane != 0) return;
   }
-  mode_store<AVG>(dst, ck * dst.sc + g * dst.sg, a);
+  mode_store<AVG>(dst, ck * dst.at.sc + g * dst.at.sg, a);
 }
 
 // The chunk tuples of a key merged in ascending chunk order into the output.
@@ -179,12 +171,13 @@ __global__ __launch_bounds__(PGPU_MODE_THREADS) void mode_combine_kernel(ModeAt 
     for (uint32_t base = 0; base < nchunks; base += 64) {
       const uint32_t ck = base + lane;
       ModeTuple b{0, 0, 0, 0, 0.0};
-      if (ck < nchunks) b = mode_load<AVG>(part, ck * part.sc + g * part.sg);
+      if (ck < nchunks) b = mode_load<AVG>(part, ck * part.at.sc + g * part.at.sg);
       a = mode_merge<AVG>(a, mode_wave<AVG>(b));
     }
     if (lane != 0) return;
   } else {
-    for (uint32_t ck = 0; ck < nchunks; ++ck) a = mode_merge<AVG>(a, mode_load<AVG>(part, ck * part.sc + g * part.sg));
+    for (uint32_t ck = 0; ck < nchunks; ++ck)
+      a = mode_merge<AVG>(a, mode_load<AVG>(part, ck * part.at.sc + g * part.at.sg));
   }
   mode_store<AVG>(out, g, a);
 }
@@ -263,16 +256,12 @@ __global__ __launch_bounds__(PGPU_MODE_THREADS) void mode_hash_kernel(const int6
   }
 }
 
-unsigned grid_of(uint64_t n) {
-  return (unsigned)std::min<uint64_t>(4096, std::max<uint64_t>(1, (n + PGPU_MODE_THREADS - 1) / PGPU_MODE_THREADS));
-}
-
 template <bool AVG>
 hipError_t launch_mode(const int64_t* in, uint64_t N, int32_t nsec, bool hash, uint64_t inner, const double* values,
                        uint64_t num_values, int64_t* mode, void* temp, int num_cus, hipStream_t st) {
   const unsigned T = PGPU_MODE_THREADS;
   const uint64_t last_value = num_values ? num_values - 1 : 0;
-  const ModeAt out{mode, mode + inner, mode + 2 * inner, mode + 3 * inner, (double*)(mode + 4 * inner), 0, 1};
+  const ModeAt out{mode, mode + inner, mode + 2 * inner, mode + 3 * inner, (double*)(mode + 4 * inner), {0, 1}};
   if (hash) {
     hipLaunchKernelGGL((mode_hash_init_kernel<AVG>), dim3(grid_of(inner)), dim3(T), 0, st, out, inner);
     if (inner == 1) {
@@ -292,13 +281,14 @@ hipError_t launch_mode(const int64_t* in, uint64_t N, int32_t nsec, bool hash, u
   const uint64_t card = N / inner;
   uint64_t chunk;
   uint32_t nchunks;
-  pgpu_select_chunks(inner, card, num_cus, &chunk, &nchunks);
+  chunks_of(inner, card, num_cus, &chunk, &nchunks);
   ModeAt dst = out;
   const bool by_wave = inner < PGPU_MODE_COMBINE_BY_WAVE;
   if (nchunks > 1) {
     int64_t* t = (int64_t*)temp;
     const uint64_t n = (uint64_t)nchunks * inner;
-    dst = ModeAt{t, t + n, t + 2 * n, t + 3 * n, (double*)(t + 4 * n), by_wave ? 1 : inner, by_wave ? nchunks : 1};
+    dst = ModeAt{t, t + n, t + 2 * n, t + 3 * n, (double*)(t + 4 * n),
+                by_wave ? PartialAt{1, nchunks} : PartialAt{inner, 1}};
   }
   const unsigned bx = (unsigned)((inner + T - 1) / T);
   if (inner < 64)
@@ -326,7 +316,7 @@ size_t pgpu_mode_temp_bytes(uint64_t N, bool hash, uint64_t inner, bool avg, int
   if (hash || inner == 0 || N == 0) return 0;
   uint64_t chunk;
   uint32_t nchunks;
-  pgpu_select_chunks(inner, N / inner, num_cus, &chunk, &nchunks);
+  chunks_of(inner, N / inner, num_cus, &chunk, &nchunks);
   return nchunks > 1 ? 8ull * (avg ? 5 : 4) * nchunks * inner : 0;
 }
 

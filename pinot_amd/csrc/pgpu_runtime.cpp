@@ -314,8 +314,9 @@ struct Workspace {
   DevMem rkctab;                       // query_kernel_rkey: container record per (leaf, id, key)
   DevMem tk_keys, tk_state;            // pgpu_table_topk: per-row order keys, radix-select state + histogram
   DevMem fold;                         // pgpu_query_collect_fold: the folded table
-  DevMem sel_tmp;                      // pgpu_query_collect_select: chunk prefixes / sorted pairs of the selection
-  DevMem mode_tmp, mode_vals;          // pgpu_query_collect_mode: chunk tuples of the mode reduction, the column's values
+  DevMem fold_tmp;                     // ... the selection's, then the mode reduction's temporary behind it: one
+                                       // buffer, since the two stages are ordered on the one stream
+  DevMem mode_vals;                    // pgpu_query_collect_mode: the column's values
   PinnedMem h_arena, h_stats, h_total, h_table, h_segcnt, h_leafbits, h_segany, h_fsment;
   PinnedMem h_fold;                    // pgpu_query_collect_fold: a small folded table, compacted on the host
   PinnedMem h_mode_vals;               // pgpu_query_collect_mode: the caller's values, staged for the copy to mode_vals
@@ -4926,139 +4927,233 @@ int pgpu_table_topk(pgpu_context* ctx, const pgpu_table_layout* layout, const vo
   return rc;
 }
 
-// ---- DISTINCTCOUNT: fold of a GROUP BY g, c table over c (include/pinot_gpu.h; kernels in pgpu_fold.hip) ------------
-int pgpu_fold_layout_of(const pgpu_table_layout* in, uint64_t inner_keys, pgpu_table_layout* out) {
-  if (!in || !out) return fail(PGPU_E_INVALID, "null argument");
+}  // extern "C"
+
+// ---- DISTINCTCOUNT, PERCENTILE, MODE: the fold of a GROUP BY g, c table over c, the rank selection and the mode -----
+// reduction behind it (include/pinot_gpu.h; kernels in pgpu_fold.hip, pgpu_select.hip, pgpu_mode.hip).  The nine entry
+// points state what they were asked for as a FoldedSpec and share one layout builder (folded_layout), one size of
+// temporary memory (folded_temp_bytes) and one enqueue (enqueue_folded).
+namespace {
+
+// Which public contract is served: the stage names the last step asked for, not what the numbers happen to be -- a
+// selection of 0 percentiles or a mode reduction with an empty mask is refused as such, never run as the step before.
+enum FoldedStage { STAGE_FOLD, STAGE_SELECT, STAGE_MODE };
+const char* const kStageTable[] = {"folded", "selected", "mode"};
+
+struct FoldedSpec {
+  FoldedStage stage = STAGE_FOLD;
+  uint64_t inner_keys = 0;
+  const double* percentiles = nullptr;  // host memory
+  int32_t num_percentiles = 0;          // STAGE_SELECT: 1..PGPU_SELECT_MAX; STAGE_MODE: 0 (no selection) as well
+  int32_t reducers = 0;                 // STAGE_MODE: a mask of PGPU_MODE_*
+  const double* values = nullptr;       // PGPU_MODE_AVG: the column's values ...
+  uint64_t num_values = 0;
+  bool values_on_device = false;        // ... in device memory (the table functions) or the caller's host memory
+
+  bool selects() const { return stage == STAGE_SELECT || (stage == STAGE_MODE && num_percentiles != 0); }
+  bool modes() const { return stage == STAGE_MODE; }
+  bool avg() const { return modes() && (reducers & PGPU_MODE_AVG) != 0; }
+};
+
+// The layout of the resulting table and where the stages write in it: sections [0, picks_at - 1) are the input's,
+// picks_at - 1 the distinct count, [picks_at, mode_at) one per percentile, [mode_at, num_sections) M, T, LO, HI (, S).
+struct FoldedLayout {
+  pgpu_table_layout layout;
+  int picks_at, mode_at;
+};
+
+// The first unused aggregation entry: all zero (a COUNT has value type -1, any other aggregation its section).
+int first_free_entry(const pgpu_table_layout& L) {
+  int n = 16;
+  while (n > 0 && L.agg_section[n - 1] == 0 && L.agg_value_type[n - 1] == 0) --n;
+  return n;
+}
+
+// n int64 results in the sections from `section` on, as the aggregation entries from `entry` on.
+void append_long_entries(pgpu_table_layout* F, int entry, int section, int n) {
+  for (int j = 0; j < n; ++j) {
+    F->agg_section[entry + j] = section + j;
+    F->agg_value_type[entry + j] = PGPU_LONG;
+    F->agg_sum_parts[entry + j] = 1;
+    F->agg_sum_exp[entry + j] = 0;
+  }
+}
+
+// Every check of the table and of the numbers of `s` (its pointers: check_operands), then the layout.
+int folded_layout(const pgpu_table_layout& in, const FoldedSpec& s, FoldedLayout* out) {
+  const int k = s.num_percentiles;
+  if (s.modes() && (s.reducers <= 0 || (s.reducers & ~(PGPU_MODE_MIN | PGPU_MODE_MAX | PGPU_MODE_AVG))))
+    return fail(PGPU_E_INVALID, "mode reducers 0x%x (a mask of PGPU_MODE_MIN, PGPU_MODE_MAX, PGPU_MODE_AVG)", s.reducers);
+  if (s.selects() && (k < 1 || k > PGPU_SELECT_MAX))
+    return fail(PGPU_E_INVALID, "%d percentiles (1..%d are selected at once)", k, PGPU_SELECT_MAX);
+  const uint64_t inner_keys = s.inner_keys;
   if (inner_keys == 0) return fail(PGPU_E_INVALID, "fold over 0 inner keys");
-  if (in->num_sections < 1 || in->num_sections > PGPU_MAX_SECTIONS)
-    return fail(PGPU_E_INVALID, "table of %d sections", in->num_sections);
-  const bool hash = in->key_kind == PGPU_KEYS_HASH;
-  if (!hash && in->num_keys % inner_keys != 0)
-    return fail(PGPU_E_INVALID, "%llu keys are no multiple of %llu inner keys", (unsigned long long)in->num_keys,
+  if (in.num_sections < 1 || in.num_sections > PGPU_MAX_SECTIONS)
+    return fail(PGPU_E_INVALID, "table of %d sections", in.num_sections);
+  const bool hash = in.key_kind == PGPU_KEYS_HASH;
+  if (!hash && in.num_keys % inner_keys != 0)
+    return fail(PGPU_E_INVALID, "%llu keys are no multiple of %llu inner keys", (unsigned long long)in.num_keys,
                 (unsigned long long)inner_keys);
-  if (hash && in->key_words == 2) return fail(PGPU_E_UNSUPPORTED, "fold of a table with two key words");
+  if (hash && in.key_words == 2) return fail(PGPU_E_UNSUPPORTED, "fold of a table with two key words");
   if (inner_keys > PGPU_FOLD_MAX_KEYS)
     return fail(PGPU_E_UNSUPPORTED, "fold into %llu keys (more than a collect returns)", (unsigned long long)inner_keys);
-  if (in->num_sections + 1 > PGPU_MAX_SECTIONS)
-    return fail(PGPU_E_UNSUPPORTED, "no section left for the distinct count (%d in use)", in->num_sections);
-  // the first unused aggregation entry: all zero (a COUNT has value type -1, any other aggregation its section)
-  int n = 16;
-  while (n > 0 && in->agg_section[n - 1] == 0 && in->agg_value_type[n - 1] == 0) --n;
-  if (n >= 16) return fail(PGPU_E_UNSUPPORTED, "no aggregation entry left for the distinct count");
-  pgpu_table_layout F = *in;
+  if (in.num_sections + 1 > PGPU_MAX_SECTIONS)
+    return fail(PGPU_E_UNSUPPORTED, "no section left for the distinct count (%d in use)", in.num_sections);
+  int entry = first_free_entry(in);
+  if (entry >= 16) return fail(PGPU_E_UNSUPPORTED, "no aggregation entry left for the distinct count");
+  pgpu_table_layout& F = out->layout;
+  F = in;
   F.num_keys = inner_keys;
   F.key_kind = PGPU_KEYS_DENSE;
   F.key_words = 1;
   F.section_op[F.num_sections] = PGPU_RED_SUM_I64;
-  F.agg_section[n] = F.num_sections;
-  F.agg_value_type[n] = PGPU_LONG;
-  F.agg_sum_parts[n] = 1;
-  F.agg_sum_exp[n] = 0;
+  append_long_entries(&F, entry, F.num_sections, 1);
+  entry += 1;
   F.num_sections += 1;
-  *out = F;
+  out->picks_at = out->mode_at = F.num_sections;
+  if (s.selects()) {
+    if (F.num_sections + k > PGPU_MAX_SECTIONS)
+      return fail(PGPU_E_UNSUPPORTED, "no section left for %d percentiles (%d in use)", k, F.num_sections);
+    if (entry + k > 16) return fail(PGPU_E_UNSUPPORTED, "no aggregation entry left for %d percentiles", k);
+    for (int j = 0; j < k; ++j) F.section_op[F.num_sections + j] = PGPU_RED_SUM_I64;
+    append_long_entries(&F, entry, F.num_sections, k);
+    entry += k;
+    F.num_sections += k;
+    out->mode_at = F.num_sections;
+  }
+  if (s.modes()) {
+    const int more = s.avg() ? 5 : 4;  // M, T, LO, HI (, S)
+    if (F.num_sections + more > PGPU_MAX_SECTIONS)
+      return fail(PGPU_E_UNSUPPORTED, "no section left for the %d mode sections (%d in use)", more, F.num_sections);
+    if (entry + 2 > 16) return fail(PGPU_E_UNSUPPORTED, "no aggregation entry left for the mode");
+    for (int j = 0; j < more; ++j) F.section_op[F.num_sections + j] = j == 4 ? PGPU_RED_SUM_F64 : PGPU_RED_SUM_I64;
+    append_long_entries(&F, entry, F.num_sections + 2, 2);  // LO and HI; M and T are sections only
+    F.num_sections += more;
+  }
   return PGPU_OK;
 }
 
-int pgpu_table_fold(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
-                    uint64_t inner_keys, void* dev_out, uint64_t out_bytes) {
-  if (!ctx || !in_layout || !dev_table || !dev_out) return fail(PGPU_E_INVALID, "null argument");
-  pgpu_table_layout F;
-  const int rc = pgpu_fold_layout_of(in_layout, inner_keys, &F);
-  if (rc) return rc;
-  if (out_bytes < pgpu_table_bytes(&F))
-    return fail(PGPU_E_INVALID, "folded table needs %llu bytes, %llu given", (unsigned long long)pgpu_table_bytes(&F),
-                (unsigned long long)out_bytes);
-  if (in_layout->num_keys == 0) return fail(PGPU_E_INVALID, "empty table");
-  HIP_TRY(hipSetDevice(ctx->device));
-  HIP_TRY(pgpu_launch_fold((const int64_t*)dev_table, in_layout->num_keys, in_layout->num_sections,
-                           in_layout->section_op, in_layout->key_kind == PGPU_KEYS_HASH, inner_keys,
-                           (int64_t*)dev_out, ctx->num_cus, (hipStream_t)stream));
-  return PGPU_OK;
+// The three public layout functions.
+int folded_layout_of(const pgpu_table_layout* in, const FoldedSpec& s, pgpu_table_layout* out) {
+  if (!in || !out) return fail(PGPU_E_INVALID, "null argument");
+  FoldedLayout fl;
+  const int rc = folded_layout(*in, s, &fl);
+  if (rc == PGPU_OK) *out = fl.layout;
+  return rc;
 }
 
-}  // extern "C"
-
-namespace {
-
-int check_percentiles(const double* percentiles, int32_t num_percentiles) {
-  if (num_percentiles < 1 || num_percentiles > PGPU_SELECT_MAX)
-    return fail(PGPU_E_INVALID, "%d percentiles (1..%d are selected at once)", num_percentiles, PGPU_SELECT_MAX);
-  if (!percentiles) return fail(PGPU_E_INVALID, "null argument");
-  for (int j = 0; j < num_percentiles; ++j)
-    if (!(percentiles[j] >= 0.0 && percentiles[j] <= 100.0))
-      return fail(PGPU_E_INVALID, "percentile %g is outside [0, 100]", percentiles[j]);
-  return PGPU_OK;
-}
-
-int check_reducers(int32_t reducers, const double* values, uint64_t num_values) {
-  if (reducers == 0 || (reducers & ~(PGPU_MODE_MIN | PGPU_MODE_MAX | PGPU_MODE_AVG)))
-    return fail(PGPU_E_INVALID, "mode reducers 0x%x (a mask of PGPU_MODE_MIN, PGPU_MODE_MAX, PGPU_MODE_AVG)", reducers);
-  if ((reducers & PGPU_MODE_AVG) && (!values || num_values == 0))
+// What folded_layout cannot see: the percentiles themselves and the values behind PGPU_MODE_AVG.
+int check_operands(const FoldedSpec& s) {
+  if (s.selects()) {
+    if (!s.percentiles) return fail(PGPU_E_INVALID, "null argument");
+    for (int j = 0; j < s.num_percentiles; ++j)
+      if (!(s.percentiles[j] >= 0.0 && s.percentiles[j] <= 100.0))
+        return fail(PGPU_E_INVALID, "percentile %g is outside [0, 100]", s.percentiles[j]);
+  }
+  if (s.avg() && (!s.values || s.num_values == 0))
     return fail(PGPU_E_INVALID, "PGPU_MODE_AVG without the column's values");
   return PGPU_OK;
 }
 
-// pgpu_query_collect_fold (num_percentiles = 0, reducers = 0), pgpu_query_collect_select (reducers = 0) and
-// pgpu_query_collect_mode: the fold, the selection and the mode reduction behind it on the same stream, then the
-// resulting table compacted or trimmed.  reducers < 0: a mode collect whose mask the layout check is to refuse.
-int collect_folded(pgpu_query* qq, uint64_t inner_keys, const double* percentiles, int32_t num_percentiles,
-                   int32_t reducers, const double* values, uint64_t num_values, const pgpu_topk* order,
-                   int64_t* out_keys, int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
-                   pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
+// Temporary bytes of enqueue_folded: the larger need of the stages present, which share the buffer.
+size_t folded_temp_bytes(const pgpu_table_layout& in, const FoldedSpec& s, int num_cus) {
+  const bool hash = in.key_kind == PGPU_KEYS_HASH;
+  size_t tb = 0;
+  if (s.selects()) tb = std::max(tb, pgpu_select_temp_bytes(in.num_keys, hash, s.inner_keys, num_cus));
+  if (s.modes()) tb = std::max(tb, pgpu_mode_temp_bytes(in.num_keys, hash, s.inner_keys, s.avg(), num_cus));
+  return tb;
+}
+
+// The device work of every folded entry point, on `st`: the fold of `table` (layout `in`) into `out` (layout
+// fl.layout), then the selection and the mode reduction of `s` into their sections of `out`.  `s` and `fl` have passed
+// folded_layout and check_operands; s.values are in device memory; temp holds folded_temp_bytes(...) bytes.
+int enqueue_folded(const pgpu_table_layout& in, const void* table, const FoldedSpec& s, const FoldedLayout& fl,
+                   void* out, void* temp, size_t temp_bytes, int num_cus, hipStream_t st) {
+  const int64_t* t = (const int64_t*)table;
+  int64_t* o = (int64_t*)out;
+  const bool hash = in.key_kind == PGPU_KEYS_HASH;
+  hipError_t e = pgpu_launch_fold(t, in.num_keys, in.num_sections, in.section_op, hash, s.inner_keys, o, num_cus, st);
+  if (e != hipSuccess) return fail(PGPU_E_HIP, "table fold: %s", hipGetErrorString(e));
+  if (s.selects()) {
+    e = pgpu_launch_select(t, in.num_keys, in.num_sections, hash, s.inner_keys, s.percentiles, s.num_percentiles, o,
+                           o + (uint64_t)fl.picks_at * s.inner_keys, temp, temp_bytes, num_cus, st);
+    if (e != hipSuccess) return fail(PGPU_E_HIP, "table select: %s", hipGetErrorString(e));
+  }
+  if (s.modes()) {
+    int64_t* mode = o + (uint64_t)fl.mode_at * s.inner_keys;
+    e = pgpu_launch_mode(t, in.num_keys, in.num_sections, hash, s.inner_keys, s.avg() ? s.values : nullptr,
+                         s.avg() ? s.num_values : 0, s.avg(), mode, temp, temp_bytes, num_cus, st);
+    if (e != hipSuccess) return fail(PGPU_E_HIP, "table mode: %s", hipGetErrorString(e));
+  }
+  return PGPU_OK;
+}
+
+// pgpu_table_fold, pgpu_table_select, pgpu_table_mode: caller-owned memory, nothing waits for the kernels.
+int table_folded(pgpu_context* ctx, const pgpu_table_layout* in, const void* dev_table, void* stream,
+                 const FoldedSpec& s, void* dev_out, uint64_t out_bytes) {
+  if (!ctx || !in || !dev_table || !dev_out) return fail(PGPU_E_INVALID, "null argument");
+  FoldedLayout fl;
+  int rc = folded_layout(*in, s, &fl);
+  if (rc == PGPU_OK) rc = check_operands(s);
+  if (rc) return rc;
+  if (out_bytes < pgpu_table_bytes(&fl.layout))
+    return fail(PGPU_E_INVALID, "%s table needs %llu bytes, %llu given", kStageTable[s.stage],
+                (unsigned long long)pgpu_table_bytes(&fl.layout), (unsigned long long)out_bytes);
+  if (in->num_keys == 0) return fail(PGPU_E_INVALID, "empty table");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  // the temporary memory is taken and given back in stream order
+  const size_t tb = folded_temp_bytes(*in, s, ctx->num_cus);
+  void* temp = nullptr;
+  if (tb) {
+    if (ctx->mpool) HIP_TRY(hipMallocFromPoolAsync(&temp, tb, ctx->mpool, st));
+    else HIP_TRY(hipMallocAsync(&temp, tb, st));
+  }
+  rc = enqueue_folded(*in, dev_table, s, fl, dev_out, temp, tb, ctx->num_cus, st);
+  if (temp) (void)hipFreeAsync(temp, st);
+  return rc;
+}
+
+// pgpu_query_collect_fold, pgpu_query_collect_select, pgpu_query_collect_mode: the wait, the pipeline on the query's
+// workspace, then the resulting table compacted or trimmed.  The query is released on every path.
+int collect_folded(pgpu_query* qq, FoldedSpec s, const pgpu_topk* order, int64_t* out_keys, int64_t* out_cells,
+                   uint64_t capacity, uint64_t* out_num_groups, pgpu_query_stats* out_stats,
+                   pgpu_table_layout* out_layout) {
   if (!qq || !qq->tws || !out_num_groups) return fail(PGPU_E_INVALID, "query was not submitted");
   // (a cancelled or timed-out query returns here: nothing is folded)
   int rc = pgpu_query_wait(qq, out_stats);
-  pgpu_table_layout F;
-  if (rc == PGPU_OK)
-    rc = reducers ? pgpu_mode_layout_of(&qq->layout, inner_keys, num_percentiles, reducers, &F)
-         : num_percentiles ? pgpu_select_layout_of(&qq->layout, inner_keys, num_percentiles, &F)
-                           : pgpu_fold_layout_of(&qq->layout, inner_keys, &F);
-  if (rc == PGPU_OK && num_percentiles) rc = check_percentiles(percentiles, num_percentiles);
-  if (rc == PGPU_OK && reducers) rc = check_reducers(reducers, values, num_values);
+  FoldedLayout fl;
+  const pgpu_table_layout& F = fl.layout;
+  if (rc == PGPU_OK) rc = folded_layout(qq->layout, s, &fl);
+  if (rc == PGPU_OK) rc = check_operands(s);
   if (rc == PGPU_OK) {
     // the table is complete (waited above): fold and compact it on the query's own workspace stream
     Workspace* ws = qq->ws;
-    const pgpu_table_layout& L = qq->layout;
+    const size_t tb = folded_temp_bytes(qq->layout, s, qq->ctx->num_cus);
     hipError_t e = ws->fold.ensure(pgpu_table_bytes(&F) + 16, qq->ctx->mpool, ws->stream);
-    if (e == hipSuccess)
-      e = pgpu_launch_fold((const int64_t*)qq->tws->table.p, L.num_keys, L.num_sections, L.section_op,
-                           L.key_kind == PGPU_KEYS_HASH, inner_keys, (int64_t*)ws->fold.p, qq->ctx->num_cus, ws->stream);
     if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table fold: %s", hipGetErrorString(e));
-    if (rc == PGPU_OK && num_percentiles) {
-      const bool hash = L.key_kind == PGPU_KEYS_HASH;
-      const size_t tb = pgpu_select_temp_bytes(L.num_keys, hash, inner_keys, qq->ctx->num_cus);
-      e = ws->sel_tmp.ensure(tb + 16, qq->ctx->mpool, ws->stream);
-      if (e == hipSuccess)
-        e = pgpu_launch_select((const int64_t*)qq->tws->table.p, L.num_keys, L.num_sections, hash, inner_keys,
-                               percentiles, num_percentiles, (const int64_t*)ws->fold.p,
-                               (int64_t*)ws->fold.p + (uint64_t)(L.num_sections + 1) * inner_keys, ws->sel_tmp.p, tb,
-                               qq->ctx->num_cus, ws->stream);
-      if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table select: %s", hipGetErrorString(e));
+    if (rc == PGPU_OK && s.stage != STAGE_FOLD) {
+      e = ws->fold_tmp.ensure(tb + 16, qq->ctx->mpool, ws->stream);
+      if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table %s: %s", s.modes() ? "mode" : "select", hipGetErrorString(e));
     }
-    if (rc == PGPU_OK && reducers) {
-      const bool hash = L.key_kind == PGPU_KEYS_HASH;
-      const bool avg = (reducers & PGPU_MODE_AVG) != 0;
-      const size_t tb = pgpu_mode_temp_bytes(L.num_keys, hash, inner_keys, avg, qq->ctx->num_cus);
-      e = ws->mode_tmp.ensure(tb + 16, qq->ctx->mpool, ws->stream);
-      if (e == hipSuccess && avg) {
-        // the caller's values are read here, into pinned memory the copy to the device may outlive this call from
-        const size_t vb = 8 * (size_t)num_values;
-        e = ws->h_mode_vals.ensure(vb);
-        if (e == hipSuccess) e = ws->mode_vals.ensure(vb, qq->ctx->mpool, ws->stream);
-        if (e == hipSuccess) {
-          memcpy(ws->h_mode_vals.p, values, vb);
-          e = hipMemcpyAsync(ws->mode_vals.p, ws->h_mode_vals.p, vb, hipMemcpyHostToDevice, ws->stream);
-        }
+    if (rc == PGPU_OK && s.avg() && !s.values_on_device) {
+      // the caller's values are read here, into pinned memory the copy to the device may outlive this call from
+      const size_t vb = 8 * (size_t)s.num_values;
+      e = ws->h_mode_vals.ensure(vb);
+      if (e == hipSuccess) e = ws->mode_vals.ensure(vb, qq->ctx->mpool, ws->stream);
+      if (e == hipSuccess) {
+        memcpy(ws->h_mode_vals.p, s.values, vb);
+        e = hipMemcpyAsync(ws->mode_vals.p, ws->h_mode_vals.p, vb, hipMemcpyHostToDevice, ws->stream);
       }
-      if (e == hipSuccess)
-        e = pgpu_launch_mode((const int64_t*)qq->tws->table.p, L.num_keys, L.num_sections, hash, inner_keys,
-                             avg ? (const double*)ws->mode_vals.p : nullptr, avg ? num_values : 0, avg,
-                             (int64_t*)ws->fold.p + (uint64_t)(F.num_sections - (avg ? 5 : 4)) * inner_keys,
-                             ws->mode_tmp.p, tb, qq->ctx->num_cus, ws->stream);
       if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table mode: %s", hipGetErrorString(e));
+      s.values = (const double*)ws->mode_vals.p;
+      s.values_on_device = true;
     }
+    if (rc == PGPU_OK)
+      rc = enqueue_folded(qq->layout, qq->tws->table.p, s, fl, ws->fold.p, ws->fold_tmp.p, tb, qq->ctx->num_cus,
+                          ws->stream);
   }
-  const bool trim = order && order->k > 0 && inner_keys > order->k;
+  const bool trim = order && order->k > 0 && s.inner_keys > order->k;
   if (rc == PGPU_OK && !trim && pgpu_table_bytes(&F) <= (8u << 20)) {
     // a small folded table with nothing to trim comes back whole into pinned host memory and is compacted here,
     // as pgpu_query_collect does with a small table: one synchronisation
@@ -5073,11 +5168,11 @@ int collect_folded(pgpu_query* qq, uint64_t inner_keys, const double* percentile
       const int64_t* t = (const int64_t*)ws->h_fold.p;
       const int nsec = F.num_sections;
       uint64_t n = 0;
-      for (uint64_t k = 0; k < inner_keys; ++k) {
+      for (uint64_t k = 0; k < s.inner_keys; ++k) {
         if (t[k] <= 0) continue;
         if (n < capacity) {
           out_keys[n] = (int64_t)k;
-          for (int sc = 0; sc < nsec; ++sc) out_cells[n * nsec + sc] = t[(size_t)sc * inner_keys + k];
+          for (int sc = 0; sc < nsec; ++sc) out_cells[n * nsec + sc] = t[(size_t)sc * s.inner_keys + k];
         }
         ++n;
       }
@@ -5099,164 +5194,53 @@ int collect_folded(pgpu_query* qq, uint64_t inner_keys, const double* percentile
 
 extern "C" {
 
-int pgpu_query_collect_fold(pgpu_query* qq, uint64_t inner_keys, const pgpu_topk* order, int64_t* out_keys,
-                            int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
-                            pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
-  return collect_folded(qq, inner_keys, nullptr, 0, 0, nullptr, 0, order, out_keys, out_cells, capacity, out_num_groups,
-                        out_stats, out_layout);
+int pgpu_fold_layout_of(const pgpu_table_layout* in, uint64_t inner_keys, pgpu_table_layout* out) {
+  return folded_layout_of(in, FoldedSpec{STAGE_FOLD, inner_keys}, out);
 }
-
-// ---- PERCENTILE: rank selection behind the fold (include/pinot_gpu.h; kernels in pgpu_select.hip) -------------------
 int pgpu_select_layout_of(const pgpu_table_layout* in, uint64_t inner_keys, int32_t num_percentiles,
                           pgpu_table_layout* out) {
-  if (!in || !out) return fail(PGPU_E_INVALID, "null argument");
-  if (num_percentiles < 1 || num_percentiles > PGPU_SELECT_MAX)
-    return fail(PGPU_E_INVALID, "%d percentiles (1..%d are selected at once)", num_percentiles, PGPU_SELECT_MAX);
-  pgpu_table_layout F;
-  const int rc = pgpu_fold_layout_of(in, inner_keys, &F);
-  if (rc) return rc;
-  if (F.num_sections + num_percentiles > PGPU_MAX_SECTIONS)
-    return fail(PGPU_E_UNSUPPORTED, "no section left for %d percentiles (%d in use)", num_percentiles, F.num_sections);
-  // the distinct count took the first unused aggregation entry: the percentiles take the ones behind it
-  int n = 16;
-  while (n > 0 && F.agg_section[n - 1] == 0 && F.agg_value_type[n - 1] == 0) --n;
-  if (n + num_percentiles > 16)
-    return fail(PGPU_E_UNSUPPORTED, "no aggregation entry left for %d percentiles", num_percentiles);
-  for (int j = 0; j < num_percentiles; ++j) {
-    F.section_op[F.num_sections] = PGPU_RED_SUM_I64;
-    F.agg_section[n + j] = F.num_sections;
-    F.agg_value_type[n + j] = PGPU_LONG;
-    F.agg_sum_parts[n + j] = 1;
-    F.agg_sum_exp[n + j] = 0;
-    F.num_sections += 1;
-  }
-  *out = F;
-  return PGPU_OK;
+  return folded_layout_of(in, FoldedSpec{STAGE_SELECT, inner_keys, nullptr, num_percentiles}, out);
+}
+int pgpu_mode_layout_of(const pgpu_table_layout* in, uint64_t inner_keys, int32_t num_percentiles, int32_t reducers,
+                        pgpu_table_layout* out) {
+  return folded_layout_of(in, FoldedSpec{STAGE_MODE, inner_keys, nullptr, num_percentiles, reducers}, out);
 }
 
+int pgpu_table_fold(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
+                    uint64_t inner_keys, void* dev_out, uint64_t out_bytes) {
+  return table_folded(ctx, in_layout, dev_table, stream, FoldedSpec{STAGE_FOLD, inner_keys}, dev_out, out_bytes);
+}
 int pgpu_table_select(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
                       uint64_t inner_keys, const double* percentiles, int32_t num_percentiles, void* dev_out,
                       uint64_t out_bytes) {
-  if (!ctx || !in_layout || !dev_table || !dev_out) return fail(PGPU_E_INVALID, "null argument");
-  pgpu_table_layout S;
-  int rc = pgpu_select_layout_of(in_layout, inner_keys, num_percentiles, &S);
-  if (rc == PGPU_OK) rc = check_percentiles(percentiles, num_percentiles);
-  if (rc) return rc;
-  if (out_bytes < pgpu_table_bytes(&S))
-    return fail(PGPU_E_INVALID, "selected table needs %llu bytes, %llu given", (unsigned long long)pgpu_table_bytes(&S),
-                (unsigned long long)out_bytes);
-  if (in_layout->num_keys == 0) return fail(PGPU_E_INVALID, "empty table");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  const bool hash = in_layout->key_kind == PGPU_KEYS_HASH;
-  const int nsec = in_layout->num_sections;
-  HIP_TRY(pgpu_launch_fold((const int64_t*)dev_table, in_layout->num_keys, nsec, in_layout->section_op, hash,
-                           inner_keys, (int64_t*)dev_out, ctx->num_cus, st));
-  // the temporary memory is taken and given back in stream order: nothing waits for the kernels
-  const size_t tb = pgpu_select_temp_bytes(in_layout->num_keys, hash, inner_keys, ctx->num_cus);
-  void* temp = nullptr;
-  if (tb) {
-    if (ctx->mpool) HIP_TRY(hipMallocFromPoolAsync(&temp, tb, ctx->mpool, st));
-    else HIP_TRY(hipMallocAsync(&temp, tb, st));
-  }
-  const hipError_t e = pgpu_launch_select((const int64_t*)dev_table, in_layout->num_keys, nsec, hash, inner_keys,
-                                          percentiles, num_percentiles, (const int64_t*)dev_out,
-                                          (int64_t*)dev_out + (uint64_t)(nsec + 1) * inner_keys, temp, tb, ctx->num_cus,
-                                          st);
-  if (temp) (void)hipFreeAsync(temp, st);
-  if (e != hipSuccess) return fail(PGPU_E_HIP, "table select: %s", hipGetErrorString(e));
-  return PGPU_OK;
+  const FoldedSpec s{STAGE_SELECT, inner_keys, percentiles, num_percentiles};
+  return table_folded(ctx, in_layout, dev_table, stream, s, dev_out, out_bytes);
 }
-
-int pgpu_query_collect_select(pgpu_query* qq, uint64_t inner_keys, const double* percentiles, int32_t num_percentiles,
-                              const pgpu_topk* order, int64_t* out_keys, int64_t* out_cells, uint64_t capacity,
-                              uint64_t* out_num_groups, pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
-  if (num_percentiles < 1) {
-    // (never the plain fold by accident: the layout check refuses it after the wait, with the query released)
-    num_percentiles = -1;
-  }
-  return collect_folded(qq, inner_keys, percentiles, num_percentiles, 0, nullptr, 0, order, out_keys, out_cells,
-                        capacity, out_num_groups, out_stats, out_layout);
-}
-
-// ---- MODE: the most frequent value behind the fold (include/pinot_gpu.h; kernels in pgpu_mode.hip) -------------------
-int pgpu_mode_layout_of(const pgpu_table_layout* in, uint64_t inner_keys, int32_t num_percentiles, int32_t reducers,
-                        pgpu_table_layout* out) {
-  if (!in || !out) return fail(PGPU_E_INVALID, "null argument");
-  if (reducers <= 0 || (reducers & ~(PGPU_MODE_MIN | PGPU_MODE_MAX | PGPU_MODE_AVG)))
-    return fail(PGPU_E_INVALID, "mode reducers 0x%x (a mask of PGPU_MODE_MIN, PGPU_MODE_MAX, PGPU_MODE_AVG)", reducers);
-  pgpu_table_layout F;
-  const int rc = num_percentiles ? pgpu_select_layout_of(in, inner_keys, num_percentiles, &F)
-                                 : pgpu_fold_layout_of(in, inner_keys, &F);
-  if (rc) return rc;
-  const bool avg = (reducers & PGPU_MODE_AVG) != 0;
-  const int more = avg ? 5 : 4;
-  if (F.num_sections + more > PGPU_MAX_SECTIONS)
-    return fail(PGPU_E_UNSUPPORTED, "no section left for the %d mode sections (%d in use)", more, F.num_sections);
-  // the distinct count and the percentiles took the first unused aggregation entries: LO and HI take the next two
-  int n = 16;
-  while (n > 0 && F.agg_section[n - 1] == 0 && F.agg_value_type[n - 1] == 0) --n;
-  if (n + 2 > 16) return fail(PGPU_E_UNSUPPORTED, "no aggregation entry left for the mode");
-  for (int j = 0; j < more; ++j) F.section_op[F.num_sections + j] = j == 4 ? PGPU_RED_SUM_F64 : PGPU_RED_SUM_I64;
-  for (int j = 0; j < 2; ++j) {  // M, T, then LO, HI
-    F.agg_section[n + j] = F.num_sections + 2 + j;
-    F.agg_value_type[n + j] = PGPU_LONG;
-    F.agg_sum_parts[n + j] = 1;
-    F.agg_sum_exp[n + j] = 0;
-  }
-  F.num_sections += more;
-  *out = F;
-  return PGPU_OK;
-}
-
 int pgpu_table_mode(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
                     uint64_t inner_keys, const double* percentiles, int32_t num_percentiles, int32_t reducers,
                     const double* dev_values, uint64_t num_values, void* dev_out, uint64_t out_bytes) {
-  if (!ctx || !in_layout || !dev_table || !dev_out) return fail(PGPU_E_INVALID, "null argument");
-  pgpu_table_layout F;
-  int rc = pgpu_mode_layout_of(in_layout, inner_keys, num_percentiles, reducers, &F);
-  if (rc == PGPU_OK && num_percentiles) rc = check_percentiles(percentiles, num_percentiles);
-  if (rc == PGPU_OK) rc = check_reducers(reducers, dev_values, num_values);
-  if (rc) return rc;
-  if (out_bytes < pgpu_table_bytes(&F))
-    return fail(PGPU_E_INVALID, "mode table needs %llu bytes, %llu given", (unsigned long long)pgpu_table_bytes(&F),
-                (unsigned long long)out_bytes);
-  if (in_layout->num_keys == 0) return fail(PGPU_E_INVALID, "empty table");
-  // the fold and the selection, as pgpu_table_fold / pgpu_table_select enqueue them
-  if (num_percentiles)
-    rc = pgpu_table_select(ctx, in_layout, dev_table, stream, inner_keys, percentiles, num_percentiles, dev_out,
-                           out_bytes);
-  else
-    rc = pgpu_table_fold(ctx, in_layout, dev_table, stream, inner_keys, dev_out, out_bytes);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const bool hash = in_layout->key_kind == PGPU_KEYS_HASH;
-  const bool avg = (reducers & PGPU_MODE_AVG) != 0;
-  // the temporary memory is taken and given back in stream order: nothing waits for the kernels
-  const size_t tb = pgpu_mode_temp_bytes(in_layout->num_keys, hash, inner_keys, avg, ctx->num_cus);
-  void* temp = nullptr;
-  if (tb) {
-    if (ctx->mpool) HIP_TRY(hipMallocFromPoolAsync(&temp, tb, ctx->mpool, st));
-    else HIP_TRY(hipMallocAsync(&temp, tb, st));
-  }
-  const hipError_t e = pgpu_launch_mode((const int64_t*)dev_table, in_layout->num_keys, in_layout->num_sections, hash,
-                                        inner_keys, avg ? dev_values : nullptr, avg ? num_values : 0, avg,
-                                        (int64_t*)dev_out + (uint64_t)(F.num_sections - (avg ? 5 : 4)) * inner_keys,
-                                        temp, tb, ctx->num_cus, st);
-  if (temp) (void)hipFreeAsync(temp, st);
-  if (e != hipSuccess) return fail(PGPU_E_HIP, "table mode: %s", hipGetErrorString(e));
-  return PGPU_OK;
+  const FoldedSpec s{STAGE_MODE, inner_keys, percentiles, num_percentiles, reducers, dev_values, num_values, true};
+  return table_folded(ctx, in_layout, dev_table, stream, s, dev_out, out_bytes);
 }
 
+int pgpu_query_collect_fold(pgpu_query* qq, uint64_t inner_keys, const pgpu_topk* order, int64_t* out_keys,
+                            int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
+                            pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
+  const FoldedSpec s{STAGE_FOLD, inner_keys};
+  return collect_folded(qq, s, order, out_keys, out_cells, capacity, out_num_groups, out_stats, out_layout);
+}
+int pgpu_query_collect_select(pgpu_query* qq, uint64_t inner_keys, const double* percentiles, int32_t num_percentiles,
+                              const pgpu_topk* order, int64_t* out_keys, int64_t* out_cells, uint64_t capacity,
+                              uint64_t* out_num_groups, pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
+  const FoldedSpec s{STAGE_SELECT, inner_keys, percentiles, num_percentiles};
+  return collect_folded(qq, s, order, out_keys, out_cells, capacity, out_num_groups, out_stats, out_layout);
+}
 int pgpu_query_collect_mode(pgpu_query* qq, uint64_t inner_keys, const double* percentiles, int32_t num_percentiles,
                             int32_t reducers, const double* values, uint64_t num_values, const pgpu_topk* order,
                             int64_t* out_keys, int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
                             pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
-  // (never the plain fold or selection by accident: the layout check refuses a bad mask or a negative number of
-  // percentiles after the wait, with the query released)
-  if (reducers == 0) reducers = -1;
-  return collect_folded(qq, inner_keys, percentiles, num_percentiles, reducers, values, num_values, order, out_keys,
-                        out_cells, capacity, out_num_groups, out_stats, out_layout);
+  const FoldedSpec s{STAGE_MODE, inner_keys, percentiles, num_percentiles, reducers, values, num_values, false};
+  return collect_folded(qq, s, order, out_keys, out_cells, capacity, out_num_groups, out_stats, out_layout);
 }
 
 }  // extern "C"

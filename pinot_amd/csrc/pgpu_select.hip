@@ -29,22 +29,17 @@
 #include <rocprim/device/device_scan_by_key.hpp>
 
 #include "../../include/pinot_gpu.h"
+#include "pgpu_axis.h"
 
-#define PGPU_SEL_THREADS 256
-#define PGPU_SEL_WAVES (PGPU_SEL_THREADS / 64)
+#define PGPU_SEL_THREADS PGPU_AXIS_THREADS
+#define PGPU_SEL_WAVES PGPU_AXIS_WAVES
 #define PGPU_SEL_UNROLL 8       // cells per thread whose counts are loaded before any is used
 #define PGPU_SEL_SCAN_BY_WAVE 4096  // inner below this: the chunk prefix of a key is taken by a wave, not a thread
-#define PGPU_SEL_MAX_CHUNKS 1024
-#define PGPU_SEL_MIN_WAVE_CHUNK 256  // cid per (g, chunk) wave at least: four steps of 64 lanes
 
 // The percentiles, by value.
 struct SelectRanks {
   double p[PGPU_SELECT_MAX];
   int32_t k;
-};
-// partial(chunk, g) is at chunk * sc + g * sg: [chunk][g] (sc = inner, sg = 1) or [g][chunk] (sc = 1, sg = nchunks).
-struct PartialAt {
-  uint64_t sc, sg;
 };
 
 namespace {
@@ -61,16 +56,6 @@ FI int64_t select_rank(int64_t n, double p) {
   return r < n ? r : n - 1;
 }
 
-FI int64_t shfl_up64(int64_t v, int d) {
-  const int lo = __shfl_up((int)(uint32_t)v, d, 64);
-  const int hi = __shfl_up((int)(uint32_t)((uint64_t)v >> 32), d, 64);
-  return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-}
-FI int64_t shfl64(int64_t v, int lane) {
-  const int lo = __shfl((int)(uint32_t)v, lane, 64);
-  const int hi = __shfl((int)(uint32_t)((uint64_t)v >> 32), lane, 64);
-  return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-}
 // Inclusive prefix sum over the wave's 64 lanes.
 FI int64_t wave_inclusive(int64_t v, int lane) {
 #pragma unroll
@@ -280,24 +265,7 @@ __global__ __launch_bounds__(PGPU_SEL_THREADS) void select_empty_kernel(const in
       for (int j = 0; j < k; ++j) sel[(uint64_t)j * inner + g] = 0;
 }
 
-unsigned grid_of(uint64_t n) {
-  return (unsigned)std::min<uint64_t>(4096, std::max<uint64_t>(1, (n + PGPU_SEL_THREADS - 1) / PGPU_SEL_THREADS));
-}
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// Chunks of cid for dense input: (chunk, nchunks).
-void chunks_of(uint64_t inner, uint64_t card, int num_cus, uint64_t* chunk, uint32_t* nchunks) {
-  const bool wave = inner < 64;
-  // a few waves per SIMD: what the keys do not give comes from splitting cid
-  const uint64_t have = wave ? inner : (inner + PGPU_SEL_THREADS - 1) / PGPU_SEL_THREADS;
-  const uint64_t want = (wave ? 32ull : 8ull) * (uint64_t)std::max(num_cus, 1);
-  const uint64_t fill = (want + have - 1) / have;
-  const uint64_t most = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(card, PGPU_SEL_MAX_CHUNKS), fill));
-  uint64_t c = (card + most - 1) / most;
-  if (wave) c = std::max<uint64_t>(PGPU_SEL_MIN_WAVE_CHUNK, (c + 63) & ~63ull);
-  *chunk = c;
-  *nchunks = (uint32_t)((card + c - 1) / c);
-}
 
 // rocPRIM's temporary bytes for the sort and the scan of N pairs.  Asked twice per selection (by the caller sizing its
 // buffer, then by the launch checking it) and with the same N query after query: the last answer is kept per thread.
@@ -316,11 +284,6 @@ size_t hash_sort_temp(uint64_t N) {
 }
 
 }  // namespace
-
-// The same cut for the mode reduction over the same axis (pgpu_mode.hip).
-void pgpu_select_chunks(uint64_t inner, uint64_t card, int num_cus, uint64_t* chunk, uint32_t* nchunks) {
-  chunks_of(inner, card, num_cus, chunk, nchunks);
-}
 
 // Temporary bytes pgpu_launch_select needs for this input (0: none).
 size_t pgpu_select_temp_bytes(uint64_t N, bool hash, uint64_t inner, int num_cus) {

@@ -928,9 +928,7 @@ class GpuPlanMaker:
         pending = []
         for p, (prep, inner, F, order) in zip(passes, ready):
             pq = self._launch(prep, segments)
-            pq.fold = (inner, F, p.folded)
-            pq.percentiles = p.percentiles
-            pq.reducers = p.reducers
+            pq.fold = FoldedPass(inner, F, p.folded, p.percentiles, p.reducers)
             pq.order = order
             pending.append(pq)
         return DistinctPending(self, query, passes, pending)
@@ -946,14 +944,8 @@ class GpuPlanMaker:
             inner = 1
             for g in globals_[:-1]:
                 inner *= len(g[0])
-            F = TableLayout()
-            if p.mode:  # ... plus the mode sections behind them
-                _lib.check(self.ctx._lib.pgpu_mode_layout_of(C.byref(L), inner, len(p.percentile), p.reducers,
-                                                             C.byref(F)))
-            elif p.percentile:  # the folded table plus one section of selected ids per percentile
-                _lib.check(self.ctx._lib.pgpu_select_layout_of(C.byref(L), inner, len(p.percentile), C.byref(F)))
-            else:
-                _lib.check(self.ctx._lib.pgpu_fold_layout_of(C.byref(L), inner, C.byref(F)))
+            # the folded table, plus one section of selected ids per percentile, plus the mode sections behind them
+            F = _lib.folded_layout_of(L, inner, len(p.percentile), p.reducers)
             order = None
             if op is not None and op[0] == pi:
                 # the trim's order over the folded table: its aggregation entries are Q's, then the distinct count
@@ -1012,7 +1004,7 @@ class GpuPlanMaker:
         L = pending.layout
         fold = pending.fold
         if fold is not None:  # a DISTINCTCOUNT pass: the rows of its table folded over the distinct column
-            L = fold[1]
+            L = fold.layout
         cap = int(min(L.num_keys, 1 << 26))
         kw = key_words_out(L)
         keys = np.empty(max(cap, 1) * kw, dtype=np.int64)
@@ -1022,33 +1014,16 @@ class GpuPlanMaker:
         h, pending.handle = pending.handle, None
         query = pending.query
         order = pending.order
-        if fold is not None and pending.reducers:  # ... with its percentiles picked and its modes reduced behind the fold
-            query = fold[2]
-            ps = (C.c_double * max(len(pending.percentiles), 1))(*pending.percentiles)
-            vals, nv = None, 0
-            if pending.reducers & _lib.PGPU_MODE_AVG:
+        if fold is not None:  # ... with its percentiles picked and its modes reduced behind the fold
+            query = fold.query
+            vals = None
+            if fold.reducers & _lib.PGPU_MODE_AVG:
                 # each value converted to double once, before any add (ModeAggregationFunction.java:558-572)
-                dv = np.ascontiguousarray(pending.globals_[-1][0], dtype=np.float64)
-                vals, nv = dv.ctypes.data_as(C.POINTER(C.c_double)), len(dv)
-            _lib.check(self.ctx._lib.pgpu_query_collect_mode(h, fold[0], ps, len(pending.percentiles), pending.reducers,
-                                                             vals, nv, C.byref(order) if order is not None else None,
-                                                             keys.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                             cells.ctypes.data_as(C.POINTER(C.c_int64)), cap,
-                                                             C.byref(n), C.byref(st), None))
-        elif fold is not None and pending.percentiles:  # ... and its percentiles picked behind the fold
-            query = fold[2]
-            ps = (C.c_double * len(pending.percentiles))(*pending.percentiles)
-            _lib.check(self.ctx._lib.pgpu_query_collect_select(h, fold[0], ps, len(ps),
-                                                               C.byref(order) if order is not None else None,
-                                                               keys.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                               cells.ctypes.data_as(C.POINTER(C.c_int64)), cap,
-                                                               C.byref(n), C.byref(st), None))
-        elif fold is not None:
-            query = fold[2]
-            _lib.check(self.ctx._lib.pgpu_query_collect_fold(h, fold[0], C.byref(order) if order is not None else None,
-                                                             keys.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                             cells.ctypes.data_as(C.POINTER(C.c_int64)), cap,
-                                                             C.byref(n), C.byref(st), None))
+                vals = np.ascontiguousarray(pending.globals_[-1][0], dtype=np.float64)
+            _lib.collect_folded(h, fold.inner_keys, fold.percentiles, fold.reducers, vals,
+                                C.byref(order) if order is not None else None,
+                                keys.ctypes.data_as(C.POINTER(C.c_int64)), cells.ctypes.data_as(C.POINTER(C.c_int64)),
+                                cap, C.byref(n), C.byref(st), None)
         else:
             _lib.check(self.ctx._lib.pgpu_query_collect_topk(h, C.byref(order) if order is not None else None,
                                                              keys.ctypes.data_as(C.POINTER(C.c_int64)),
@@ -1179,6 +1154,16 @@ class GpuPlanMaker:
 
 
 @dataclass
+class FoldedPass:
+    """What the collect of a folded pass needs (_lib.collect_folded)."""
+    inner_keys: int
+    layout: TableLayout  # of the folded table (_lib.folded_layout_of)
+    query: QueryContext  # the folded query: what the rows of that table answer
+    percentiles: list  # picked behind the fold (pgpu_query_collect_select) ...
+    reducers: int  # ... and the reducer mask of the mode reduction behind them (pgpu_query_collect_mode), 0: none
+
+
+@dataclass
 class PendingQuery:
     """A submitted, not yet collected query (owns the libpinotgpu query handle)."""
     maker: "GpuPlanMaker"
@@ -1190,9 +1175,7 @@ class PendingQuery:
     mv: Optional[tuple] = None  # (original query, lowered aggregation indexes) when *MV aggregations were lowered
     matched: Optional[np.ndarray] = None  # per-segment matched flags, filled by the wait (pgpu_query_matched_segments)
     order: Optional[object] = None  # the pgpu_topk given at submit (collect passes the same one)
-    fold: Optional[tuple] = None  # a folded (DISTINCTCOUNT / PERCENTILE) pass: (inner keys, folded layout, folded query)
-    percentiles: Optional[list] = None  # ... and the percentiles picked behind its fold (pgpu_query_collect_select)
-    reducers: int = 0  # ... and the reducer mask of the mode reduction behind them (pgpu_query_collect_mode)
+    fold: Optional["FoldedPass"] = None  # a DISTINCTCOUNT / PERCENTILE / MODE pass: collected through the fold
 
     def cancel(self) -> None:
         """Stop the query (pgpu_query_cancel): its kernels skip their remaining tiles and collect raises

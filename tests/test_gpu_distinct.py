@@ -445,7 +445,7 @@ def test_cancelled_pass_is_not_folded_and_the_context_stays_usable(gpu_ctx, thre
     pending = pm.submit(q, gs)
     pending.cancel()
     (pq,) = pending.pending
-    inner, F, _ = pq.fold
+    inner, F = pq.fold.inner_keys, pq.fold.layout
     keys = (C.c_int64 * inner)()
     cells = (C.c_int64 * (inner * F.num_sections))()
     n = C.c_uint64()

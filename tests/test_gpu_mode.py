@@ -540,7 +540,46 @@ def test_forced_hash_path(gpu_ctx, three):
         parse_sql(SEL + "g, SUM(x), PERCENTILE50(c_int) FROM t WHERE f < 30 GROUP BY g LIMIT 100"), gs).group_rows
 
 
-# ---- 3. the large key paths ---------------------------------------------------------------------------------------------
+def _pct(values, p):
+    """PercentileAggregationFunction.java:152-165 over the collected values (p < 100)."""
+    s = np.sort(values)
+    return float(s[int(float(len(s)) * p / 100.0)])
+
+
+def _avg_bound(values):
+    """test_table_mode_dense_sum_of_doubles_is_bounded_and_reproducible's bound on S, (T - 1) 2^-53 sum|v| over the T
+    tied values, carried to the reducer's S / T.  (c_int's values and their sums are integers exact in double, so S / T
+    is the same division on both sides and the bound covers the adds alone.)"""
+    tied = _modes(values).astype(np.float64)
+    return (len(tied) - 1) * 2.0 ** -53 * math.fsum(np.abs(tied)) / len(tied)
+
+
+@pytest.mark.parametrize("hashed", [False, True], ids=["dense", "hash"])
+@pytest.mark.parametrize("grouped", [False, True], ids=["agg", "group"])
+def test_selection_and_mode_reduction_share_the_collect_temporary(gpu_ctx, three, grouped, hashed):
+    """The selection and the mode reduction of one collect take their temporaries from one workspace buffer, one after
+    the other on the stream.  Aggregation only (inner = 1) and GROUP BY g (inner = 7) cut the ~3,000 ids into several
+    chunks, so on dense input both stages use it (chunk prefixes, then chunk tuples); on hash input the selection's
+    sort buffers fill it and the mode reduction needs none.  Twice on one plan maker: the second collect meets what
+    the first left in the buffer."""
+    gs, host = three
+    pm = GpuPlanMaker(gpu_ctx, query_flags=PGPU_Q_HASH) if hashed else GpuPlanMaker(gpu_ctx)
+    q = parse_sql(SEL + ("g, " if grouped else "") + "DISTINCTCOUNT(c_int), PERCENTILE(c_int, 50), "
+                  "PERCENTILE(c_int, 99), MODE(c_int), MODE(c_int, 'AVG') FROM t" +
+                  (" GROUP BY g LIMIT 100" if grouped else ""))
+    c = host["c_int"]
+    groups = {int(k): c[host["g"] == k] for k in np.unique(host["g"])} if grouped else {None: c}
+    exact = {k: (len(np.unique(v)), _pct(v, 50), _pct(v, 99), _mode(v, "MIN")) for k, v in groups.items()}
+    for _ in range(2):
+        res, layouts = _run(pm, q, gs)
+        assert len(layouts) == 1 and layouts[0].key_kind == (PGPU_KEYS_HASH if hashed else PGPU_KEYS_DENSE)
+        rows = {r[0]: r[1:] for r in res.group_rows} if grouped else {None: tuple(res.aggregation_result)}
+        assert {k: r[:4] for k, r in rows.items()} == exact
+        for k, v in groups.items():
+            assert abs(rows[k][4] - _mode(v, "AVG")) <= _avg_bound(v), k
+
+
+# ---- 3. the large key paths -----------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def wide(gpu_ctx):
     rng = np.random.default_rng(7)
@@ -613,8 +652,8 @@ def test_cancelled_pass_is_not_reduced_and_the_context_stays_usable(gpu_ctx, thr
     pending = pm.submit(q, gs)
     pending.cancel()
     (pq,) = pending.pending
-    inner, F, _ = pq.fold
-    assert pq.reducers == ALL and F.num_sections == pq.layout.num_sections + 1 + 5
+    inner, F = pq.fold.inner_keys, pq.fold.layout
+    assert pq.fold.reducers == ALL and F.num_sections == pq.layout.num_sections + 1 + 5
     keys = (C.c_int64 * inner)()
     cells = (C.c_int64 * (inner * F.num_sections))()
     n = C.c_uint64()

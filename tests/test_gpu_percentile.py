@@ -501,8 +501,8 @@ def test_cancelled_pass_is_not_selected_and_the_context_stays_usable(gpu_ctx, th
     pending = pm.submit(q, gs)
     pending.cancel()
     (pq,) = pending.pending
-    inner, S, _ = pq.fold
-    assert pq.percentiles == [50.0] and S.num_sections == pq.layout.num_sections + 2
+    inner, S = pq.fold.inner_keys, pq.fold.layout
+    assert pq.fold.percentiles == [50.0] and S.num_sections == pq.layout.num_sections + 2
     keys = (C.c_int64 * inner)()
     cells = (C.c_int64 * (inner * S.num_sections))()
     n = C.c_uint64()
