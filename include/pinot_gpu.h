@@ -171,9 +171,11 @@ int pgpu_segment_add_docid_column(pgpu_segment* seg, int32_t column);
 /* HBM bytes held by the segment (all columns, including padding and container directories). */
 int pgpu_segment_device_bytes(const pgpu_segment* seg, uint64_t* out_bytes);
 /* The same, by kind: the reference's own indexes (forward incl. raw values, dictionary, sorted, inverted,
- * multi-value) and the derived copies seal builds (bit-sliced forward indexes, value planes). */
+ * multi-value), the derived copies seal builds (bit-sliced forward indexes, value planes) and the presence rows
+ * queries have had built since (appended behind `total`, which includes them). */
 typedef struct {
   uint64_t forward, dictionary, sorted, inverted, multi_value, sliced, value_planes, total;
+  uint64_t presence; /* tile presence rows built so far (see pgpu_presence_model); part of `total` */
 } pgpu_segment_bytes;
 int pgpu_segment_device_bytes_ex(const pgpu_segment* seg, pgpu_segment_bytes* out);
 /* ---- HBM residency of derived copies (IndexLoadingConfig seam) -------------------------------------------------
@@ -818,6 +820,40 @@ int pgpu_lead_model(int32_t bits_a, double rho_dense, int32_t residual_kind, int
                     double sel_b, const uint32_t* runs, int32_t num_runs, pgpu_lead_model_out* out);
 int64_t pgpu_lead_switch_bytes(void);
 int32_t pgpu_lead_switch(double saved_bytes, int64_t threshold_bytes);
+
+/* ---- register-direct tile skip: presence rows and the planner's model (host only, no device needed) ---------
+ * A bit-sliced fixed-bit column can carry tile presence rows: 16,384 bitmaps over the segment's 2048-doc tiles, a
+ * tile's bit set in row r when one of its docs has a dict id x with r among pgpu_presence_rows(x) -- a 16,384-bit
+ * Bloom filter per tile with 4 probes, stored bit-sliced over tiles, 1 byte of HBM per doc.  When a child of a
+ * segment's top-level AND is one non-negated scan leaf matching n <= 4 single dict ids, a tile can hold a match only
+ * if for some id all 4 of its rows have the tile's bit: query_kernel_rdirect then streams only those tiles.  No
+ * false negatives: results are the same bits, and a skipped tile adds nothing to numEntriesScannedInFilter (an index
+ * lookup scans no entries).
+ *   keep = min(1, n (1 - (1 - 1/card)^2048) + n fpr),  fpr = (1 - exp(-4 d / 16384))^4,  d = min(2048, card)
+ * is the modelled share of tiles kept.  A query skips when its launch ends on PGPU_KV_RDIRECT, carries no
+ * PGPU_Q_EXACT_FILTER_STATS, and the segments that have rows save
+ *   sum tiles (1 - keep) bytes_per_tile - probe bytes >= pgpu_presence_switch_bytes()
+ * (bytes_per_tile: the planes the chosen plan streams per tile; probe bytes: 4 n row slices per segment).  The
+ * threshold is PGPU_PRESENCE_SWITCH_BYTES, default pgpu_lead_switch_bytes()'s 32 MiB (0: whenever it saves,
+ * negative: never).
+ * The rows are built on use: every (segment, column) counts the submits whose plan would have skipped with the rows
+ * present, and the PGPU_PRESENCE_AFTER-th (default 2) is the trigger: when that query is collected
+ * (pgpu_query_wait and every collect) after running to its end -- not cancelled, not past its deadline -- the build
+ * is enqueued on a stream of its own, so it runs beside no kernel of the query that asked for it.  Later submits use
+ * the rows once the build has finished, and none waits for it; pgpu_segment_release waits for a build in flight.
+ * 0: built inside pgpu_segment_seal, for every column that has a bit-sliced copy (1 byte per doc each: for tests);
+ * negative: never built, never used.  The bytes come out of the derived-copy budget (pgpu_context_set_derived_budget); a column
+ * whose rows do not fit is not asked again. */
+void pgpu_presence_rows(int32_t id, uint16_t out[4]);
+typedef struct pgpu_presence_model_out {
+  double keep;          /* modelled share of tiles kept */
+  double saved_bytes;   /* tiles (1 - keep) bytes_per_tile - probe bytes */
+  int32_t skip;         /* saved_bytes reaches the threshold */
+  int32_t reserved;
+} pgpu_presence_model_out;
+int pgpu_presence_model(int32_t card, int32_t num_ids, int64_t tiles, double bytes_per_tile, int64_t threshold_bytes,
+                        pgpu_presence_model_out* out);
+int64_t pgpu_presence_switch_bytes(void);
 
 /* MIN/MAX order-preserving key -> double (value_type = stored type of the aggregated column). */
 double pgpu_decode_minmax_key(int64_t key, int32_t value_type);

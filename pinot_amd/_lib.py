@@ -114,7 +114,7 @@ class TableLayout(C.Structure):
 class SegmentBytes(C.Structure):
     """pgpu_segment_bytes: HBM bytes of a segment by kind (pgpu_segment_device_bytes_ex)."""
     _fields_ = [(n, C.c_uint64) for n in ("forward", "dictionary", "sorted", "inverted", "multi_value", "sliced",
-                                           "value_planes", "total")]
+                                           "value_planes", "total", "presence")]
 
 
 # pgpu_query_stats.kernel_variant
@@ -174,6 +174,24 @@ def lead_model(bits_a: int, rho_dense: float, residual_kind: int, num_dense_scan
     check(load().pgpu_lead_model(bits_a, rho_dense, residual_kind, num_dense_scans, bits_b, sel_b, flat, len(runs),
                                  C.byref(out)))
     return out
+
+
+class PresenceModelOut(C.Structure):
+    _fields_ = [("keep", C.c_double), ("saved_bytes", C.c_double), ("skip", C.c_int32), ("reserved", C.c_int32)]
+
+
+def presence_model(card: int, num_ids: int, tiles: int, bytes_per_tile: float, threshold_bytes: int) -> PresenceModelOut:
+    """pgpu_presence_model: the planner's model of skipping tiles by a column's presence rows (host only)."""
+    out = PresenceModelOut()
+    check(load().pgpu_presence_model(card, num_ids, tiles, bytes_per_tile, threshold_bytes, C.byref(out)))
+    return out
+
+
+def presence_rows(dict_id: int):
+    """pgpu_presence_rows: the four presence rows of a dict id."""
+    out = (C.c_uint16 * 4)()
+    load().pgpu_presence_rows(dict_id, out)
+    return [int(x) for x in out]
 
 
 # exported symbols and their signatures: (name, restype, argtypes)
@@ -274,6 +292,10 @@ SIGNATURES = [
                                   C.POINTER(C.c_uint32), C.c_int32, C.POINTER(LeadModelOut)]),
     ("pgpu_lead_switch_bytes", C.c_int64, []),
     ("pgpu_lead_switch", C.c_int32, [C.c_double, C.c_int64]),
+    ("pgpu_presence_rows", None, [C.c_int32, C.POINTER(C.c_uint16)]),
+    ("pgpu_presence_model", C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_int64,
+                                      C.POINTER(PresenceModelOut)]),
+    ("pgpu_presence_switch_bytes", C.c_int64, []),
 ]
 
 _lib = None

@@ -177,8 +177,37 @@ struct DevSeg {
   int32_t unit_begin;
   int32_t inv_leaf[PGPU_PREBITS];
   int32_t cand_leaf;
-  int32_t pad5_[2];
+  // register-direct tile skip (DevParams::rd_skip): the presence rows of the skip child's column (nullptr: every
+  // tile of the segment is kept), the words per row, and for each of the child's skip_n dict ids its
+  // PGPU_PRESENCE_PROBES rows -- a tile can hold id i only when its bit is set in all of skip_row[i]
+  int32_t skip_n;
+  int32_t skip_wpr;
+  const uint32_t* skip_rows;
+  uint16_t skip_row[PGPU_SLICE_RANGES][4];
 };
+static_assert(sizeof(DevSeg) % 8 == 0, "DevSeg holds pointers: the arena packs them back to back");
+
+// ---- tile presence rows (pgpu_presence.hip) ---------------------------------------------------------------------
+// A derived copy per (segment, bit-sliced fixed-bit column): PGPU_PRESENCE_ROWS bitmaps over the segment's tiles
+// ("rows" of ceil(ntiles / 32) words, zero padded).  Bit t & 31 of word t >> 5 of row r is set iff some doc below
+// num_docs of tile t has a dict id x with pgpu_presence_row_of(x, j) == r for some probe j: a Bloom filter per tile,
+// stored bit-sliced over tiles, so that "which tiles can hold id x" is the AND of PGPU_PRESENCE_PROBES rows.
+#define PGPU_PRESENCE_ROWS 16384
+#define PGPU_PRESENCE_PROBES 4
+static_assert(PGPU_PRESENCE_PROBES == 4, "DevSeg::skip_row");
+// four fixed odd multipliers (multiplicative hashing: the product's top 14 bits)
+#define PGPU_PRESENCE_M0 0x9E3779B1u
+#define PGPU_PRESENCE_M1 0x85EBCA6Bu
+#define PGPU_PRESENCE_M2 0xC2B2AE35u
+#define PGPU_PRESENCE_M3 0x27D4EB2Fu
+// Launches of query_kernel_rdirect that have a tile-skip build: no prefix planes and at most 12 leaf planes (with
+// more per tile in flight the skip loop's state would pass 128 VGPRs, one wave per SIMD less)
+#define PGPU_RD_SKIP_OK(planes, pfx) ((pfx) == 0 && (planes) <= 12)
+inline bool pgpu_rd_skip_ok(int rd_planes, int rd_pfx) { return PGPU_RD_SKIP_OK(rd_planes, rd_pfx); }
+__host__ __device__ inline uint32_t pgpu_presence_row_of(uint32_t x, int j) {
+  const uint32_t m = j == 0 ? PGPU_PRESENCE_M0 : j == 1 ? PGPU_PRESENCE_M1 : j == 2 ? PGPU_PRESENCE_M2 : PGPU_PRESENCE_M3;
+  return (uint32_t)(x * m) >> 18;
+}
 #define PGPU_PFX_PLANES 3  // top bit planes of the residual column streamed beside the fast leaf (DevParams::rd_pfx)
 
 // Filter instruction with statically resolved mask slots.
@@ -431,6 +460,9 @@ struct DevParams {
   int32_t rd_planes;              // register-direct: planes per tile held in VGPRs (>= every leaf's width; 8/10/12/16)
   int32_t mv_gmask;               // bit g: group column g is multi-value (sparse_agg_mv expands each doc's values)
   int32_t rd_pfx;                 // register-direct: prefix planes of every segment's residual leaf (0 or PGPU_PFX_PLANES)
+  int32_t rd_skip;                // register-direct: > 0: a wave handles only the tiles the segments' presence rows keep
+                                  // (DevSeg::skip_rows; one figure per launch, a segment without rows keeps every
+                                  // tile), and makes their keep bits this many row words at a time (1 .. 64)
   int32_t rs_vplanes;             // register streaming (direct == PGPU_KV_RSTREAM): value planes held per tile (16 or 24)
   int32_t total_units;            // query_kernel_rkey: (segment, 65,536-doc container key) units; query_kernel_cand:
                                   // (segment, container) units

@@ -2849,7 +2849,100 @@ FI uint32_t rd_prefix(const SegState& ss, const uint32_t (&y)[PK], uint32_t mm, 
   return mm & pm;
 }
 
-template <int MODE, int PL, int PK>
+template <int S>
+struct RdSlot {  // a ring slot as a type (rdirect_consumer's skip loop)
+  static constexpr int value = S;
+};
+// Tile skip (DevParams::rd_skip): the wave's kept tiles, in order.  The wave's tiles are those at cidx + NW j of the
+// workgroup's range [t0, tend); kept are the ones whose bit the segment's presence rows have for some id in all of
+// its PGPU_PRESENCE_PROBES rows (a segment without rows keeps every tile).  The keep bits are made a chunk of
+// p.rd_skip words (64 = 2048 tiles unless PGPU_PRESENCE_CHUNK_WORDS says less: tests reach the second chunk that
+// way) of one segment at a time -- lane l holds word cw0 + l; the lanes whose word lies in the range fetch its row
+// words together, one round trip per chunk, none per tile -- and handed out bit by bit from the lanes' registers.
+// The issue cursor of rdirect_consumer draws from here; the consume cursor follows it through the ring's slots.
+struct RdSkip {
+  int seg, tb, nt;  // the current segment, its first global tile and its tile count
+  int a, b;         // the workgroup's range within it, as tiles of the segment: [a, b)
+  int cw0;          // first word of the current chunk
+  uint32_t kw;      // this lane's keep word (bits handed out are cleared)
+  uint64_t live;    // lanes whose kw != 0
+};
+FI void rd_skip_enter(const DevParams& p, RdSkip& g, int seg, int t0, int tend) {
+  g.seg = seg;
+  g.tb = cld(&p.segs[seg].tile_begin);
+  g.nt = cld(&p.segs[seg].ntiles);
+  g.a = max(t0 - g.tb, 0);
+  g.b = min(tend - g.tb, g.nt);
+  g.cw0 = (g.a >> 5) - p.rd_skip;  // (rd_skip_next steps to the first chunk)
+  g.kw = 0u;
+  g.live = 0ull;
+}
+template <int NW>
+FI void rd_skip_chunk(const DevParams& p, RdSkip& g, int cidx, int t0, int64_t& dense_bytes) {
+  static_assert(NW == 4, "a wave's tiles are every 4th bit of a keep word");
+  const DevSeg* sg = p.segs + g.seg;
+  const int wi = g.cw0 + lane_id(), s = g.a - 32 * wi, e = g.b - 32 * wi;
+  const uint32_t range = (e <= 0 || s >= 32 || lane_id() >= p.rd_skip) ? 0u
+                         : ((e >= 32 ? ~0u : ((1u << e) - 1u)) & (s <= 0 ? ~0u : ~((1u << s) - 1u)));
+  uint32_t kw = range & (0x11111111u << ((cidx + t0 - g.tb) & 3));
+  const uint32_t* rows = (const uint32_t*)cld(&sg->skip_rows);
+  if (rows) {
+    const int n = cld(&sg->skip_n), wpr = cld(&sg->skip_wpr);
+    const uint32_t wic = (uint32_t)(wi < wpr ? wi : wpr - 1);  // (a row's address stays scalar, the lane adds its word)
+    // two ids' rows per round trip (an id past n reads id 0's again): selects behind the loads, no branch around them
+    static_assert(PGPU_SLICE_RANGES % 2 == 0, "ids are probed in pairs");
+    uint32_t keep = 0u;
+    if (kw != 0u) {  // (only the lanes whose word holds a tile of the wave in the range)
+      for (int i0 = 0; i0 < n; i0 += 2) {
+        uint32_t v[2][PGPU_PRESENCE_PROBES];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int id = i0 + i < n ? i0 + i : 0;
+          const uint32_t r01 = cld((const uint32_t*)&sg->skip_row[id][0]);
+          const uint32_t r23 = cld((const uint32_t*)&sg->skip_row[id][2]);
+          v[i][0] = (rows + (size_t)(r01 & 0xFFFFu) * wpr)[wic];
+          v[i][1] = (rows + (size_t)(r01 >> 16) * wpr)[wic];
+          v[i][2] = (rows + (size_t)(r23 & 0xFFFFu) * wpr)[wic];
+          v[i][3] = (rows + (size_t)(r23 >> 16) * wpr)[wic];
+        }
+        keep |= (v[0][0] & v[0][1] & v[0][2] & v[0][3]) | (v[1][0] & v[1][1] & v[1][2] & v[1][3]);
+      }
+    }
+    kw &= wi < wpr ? keep : 0u;
+    if ((p.flags & PGPU_FLAG_STATS) && lane_id() == 0) {  // the row words of the chunk's part of [a, b)
+      const int w0 = max(g.cw0, g.a >> 5), w1 = min(g.cw0 + p.rd_skip - 1, (g.b - 1) >> 5);
+      if (w1 >= w0) dense_bytes += (int64_t)(w1 - w0 + 1) * n * PGPU_PRESENCE_PROBES * 4;
+    }
+  }
+  g.kw = kw;
+  g.live = __builtin_amdgcn_ballot_w64(kw != 0u);
+}
+// The next kept tile of the wave (false: none left, and none on any later call).
+template <int NW>
+FI bool rd_skip_next(const DevParams& p, RdSkip& g, int cidx, int t0, int tend, int& seg, int& tile_in_seg,
+                     int64_t& dense_bytes) {
+  for (;;) {
+    if (g.live) {
+      const int l = __builtin_ctzll(g.live);
+      const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)g.kw, l);
+      if (lane_id() == l) g.kw &= g.kw - 1u;
+      if ((w & (w - 1u)) == 0u) g.live &= g.live - 1ull;
+      seg = g.seg;
+      tile_in_seg = ((g.cw0 + l) << 5) + __builtin_ctz(w);
+      return true;
+    }
+    g.cw0 += p.rd_skip;
+    if ((g.cw0 << 5) >= g.b) {  // the segment's part of the range is done
+      if (g.tb + g.nt >= tend || g.seg + 1 >= p.nseg) return false;
+      rd_skip_enter(p, g, g.seg + 1, t0, tend);
+      g.cw0 += p.rd_skip;
+      if ((g.cw0 << 5) >= g.b) continue;  // (a segment without tiles)
+    }
+    rd_skip_chunk<NW>(p, g, cidx, t0, dense_bytes);
+  }
+}
+
+template <int MODE, int PL, int PK, bool SK>
 FI Stats rdirect_consumer(const DevParams& p, const Lds& L, int cidx, int t0, int ntiles, Prof& pf) {
   constexpr int NW = PGPU_DIRECT_WAVES, RD = PGPU_RDIRECT_DEPTH;
   const int64_t t_start = now(pf);
@@ -2874,7 +2967,89 @@ FI Stats rdirect_consumer(const DevParams& p, const Lds& L, int cidx, int t0, in
   int qn = 0, qt = 0;
   SegState ss;
   int cseg = -1;
-  if (cidx < ntiles) {
+  if constexpr (SK) {
+    if (ntiles > 0) {
+      // Tile skip: the issue side draws the wave's kept tiles from rd_skip_next and leaves each one's segment and tile
+      // with its ring slot, where the consume side finds them -- one kept sequence for both.  How many tiles the wave
+      // has is not known up front: a slot without a tile ends the loop.  The rest is the loop below.
+      const int tend = t0 + ntiles;
+      RdSkip g;
+      rd_skip_enter(p, g, cursor_at(p, t0).seg, t0, tend);
+      RdIssue is;
+      int iseg = -1;
+      uint32_t x[RD][PL];
+      uint32_t y[RD][PK > 0 ? PK : 1];
+      int kseg[RD], ktile[RD];
+      bool kv[RD];
+#pragma unroll
+      for (int s = 0; s < RD; ++s) {
+        kseg[s] = ktile[s] = 0;
+        kv[s] = rd_skip_next<NW>(p, g, cidx, t0, tend, kseg[s], ktile[s], dense_bytes);
+        if (kv[s]) {
+          if (kseg[s] != iseg) rd_load_issue(p, iseg = kseg[s], is);
+          rd_load_tile(is, ktile[s], x[s]);
+          if constexpr (PK > 0) rd_load_prefix<PK>(is, ktile[s], y[s]);
+        }
+      }
+      int poll = p.cancel_poll;
+      bool stop = false;
+      // one ring slot's turn (the slot is a constant: the planes stay in registers); false: the wave is done
+      auto turn = [&](auto slot) -> bool {
+          constexpr int s = decltype(slot)::value;
+          if (!kv[s]) return false;
+          if (--poll == 0) {
+            poll = p.cancel_poll;
+            if (query_cancelled(p)) {
+              stop = true;
+              return false;
+            }
+          }
+          const int tseg = kseg[s], ttile = ktile[s];
+          if (qn && (qn >= PGPU_CQ_FLUSH || qt >= PGPU_CQ_TILES || tseg != cseg)) {
+            const int64_t tq = now(pf);
+            flush_queue<MODE, NW>(p, L, cv, la, ss, qn, matched, scanned, sector_bytes, dense_bytes, pf);
+            PROF_ADD(pf, PGPU_P_C_FLUSH, tq);
+            qn = qt = 0;
+          }
+          if (tseg != cseg) {
+            cseg = tseg;
+            load_seg(p, cseg, ss);
+          }
+          const int64_t tf = now(pf);
+#ifdef PGPU_PROFILE_BUILD
+          if (pf.on) pf.t[PGPU_P_C_TILES] += 1;
+#endif
+          const int doc0 = ttile * WT;
+          uint32_t valid;
+          {
+            const int ndocs = min(WT, ss.num_docs - doc0);
+            const int rem = ndocs - 32 * lane;
+            valid = rem >= 32 ? 0xFFFFFFFFu : (rem <= 0 ? 0u : ((1u << rem) - 1u));
+            if ((p.flags & PGPU_FLAG_STATS) && lane == 0)
+              dense_bytes += ((int64_t)ndocs * (ss.f_bits[0] - cld(&ss.sg->f_plane0) + PK) + 7) / 8;
+          }
+          uint32_t mm = rd_filter(ss, x[s], valid, lane_scanned);
+          if constexpr (PK > 0) mm = rd_prefix<PK>(ss, y[s], mm, lane_scanned);
+          // refill this register slot with the wave's next kept tile
+          kv[s] = rd_skip_next<NW>(p, g, cidx, t0, tend, kseg[s], ktile[s], dense_bytes);
+          if (kv[s]) {
+            if (kseg[s] != iseg) rd_load_issue(p, iseg = kseg[s], is);
+            rd_load_tile(is, ktile[s], x[s]);
+            if constexpr (PK > 0) rd_load_prefix<PK>(is, ktile[s], y[s]);
+          }
+          PROF_ADD(pf, PGPU_P_C_FILTER, tf);
+          const int64_t ta = now(pf);
+          direct_candidates<MODE, NW>(p, L, cv, la, ss, ttile, mm, qn, qt, lane_matched, matched, scanned, sector_bytes,
+                                      dense_bytes, pf);
+          PROF_ADD(pf, PGPU_P_C_AGG, ta);
+          return true;
+      };
+      static_assert(RD == 2, "the ring's turns are written out");
+      while (turn(RdSlot<0>{}) && turn(RdSlot<1>{})) {
+      }
+      if (qn && !stop) flush_queue<MODE, NW>(p, L, cv, la, ss, qn, matched, scanned, sector_bytes, dense_bytes, pf);
+    }
+  } else if (cidx < ntiles) {
     const int own = (ntiles - cidx + NW - 1) / NW;  // this wave's tiles: cidx, cidx + NW, ...
     Cursor ci = cursor_at(p, t0 + cidx), cur = ci;
     RdIssue is;
@@ -2965,8 +3140,8 @@ FI Stats rdirect_consumer(const DevParams& p, const Lds& L, int cidx, int t0, in
   return st;
 }
 
-template <int MODE, int PL, int PK>
-__global__ __launch_bounds__(PGPU_DIRECT_THREADS) void query_kernel_rdirect(DevParams p) {
+template <int MODE, int PL, int PK, bool SK>
+FI void rdirect_kernel(const DevParams& p) {
   constexpr int NT = PGPU_DIRECT_THREADS, NWAVES = PGPU_DIRECT_WAVES;
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
   const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2988,10 +3163,24 @@ __global__ __launch_bounds__(PGPU_DIRECT_THREADS) void query_kernel_rdirect(DevP
 #pragma unroll
   for (int k = 0; k < PGPU_NPROF; ++k) pf.t[k] = 0;
 #endif
-  const Stats st = rdirect_consumer<MODE, PL, PK>(p, L, wave, t0, t1 - t0, pf);
+  const Stats st = rdirect_consumer<MODE, PL, PK, SK>(p, L, wave, t0, t1 - t0, pf);
   direct_epilogue<MODE>(p, L, st, wave, lane, pf);
   if constexpr (MODE == PGPU_MODE_AGG || MODE == PGPU_MODE_LDS || MODE == PGPU_MODE_GLOBAL)
     if (p.fuse) fused_finalize<MODE>(p, dyn_smem);
+}
+template <int MODE, int PL, int PK>
+__global__ __launch_bounds__(PGPU_DIRECT_THREADS) void query_kernel_rdirect(DevParams p) {
+  rdirect_kernel<MODE, PL, PK, false>(p);
+}
+// The tile-skip build (DevParams::rd_skip).  A kernel of its own because both loops in one cost the plain one its
+// registers (130-134 VGPRs and 760-894 spilled SGPRs where it has 120-123 and 335-358 alone); the occupancy the plain
+// kernel reaches unasked (tests/test_kernel_resources.py) is stated here, since the generator's state sits on top.
+// Built without prefix planes and up to 12 planes (PGPU_RD_SKIP_OK): the wider variants would pass 128 VGPRs.
+template <int MODE, int PL>
+__global__ __launch_bounds__(PGPU_DIRECT_THREADS)
+__attribute__((amdgpu_waves_per_eu(MODE == PGPU_MODE_AGG ? 3 : 4))) void query_kernel_rdirect_skip(DevParams p) {
+  static_assert(PGPU_RD_SKIP_OK(PL, 0), "variant list");
+  rdirect_kernel<MODE, PL, 0, true>(p);
 }
 
 // ================================================================================================================
@@ -5658,26 +5847,45 @@ __global__ void node_merge_kernel(const int64_t* rows, uint64_t n, int32_t kw, i
 // ---- host-side launch helpers (called by pgpu_runtime.cpp) --------------------------------------------------------
 template <int M, int PL, int PK>
 static hipError_t rd_attr(size_t lds_bytes) {
-  return hipFuncSetAttribute((const void*)query_kernel_rdirect<M, PL, PK>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)lds_bytes);
+  hipError_t e = hipFuncSetAttribute((const void*)query_kernel_rdirect<M, PL, PK>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  if constexpr (PGPU_RD_SKIP_OK(PL, PK))
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void*)query_kernel_rdirect_skip<M, PL>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_bytes);
+  return e;
 }
 // (the prefix variants stop at 12 planes: 16 + 3 planes per tile in flight would pass 128 VGPRs -- one wave per
 // SIMD less -- so the runtime sets rd_pfx only for fast leaves of <= 12 bits)
 // ev0 / ev1 (both or neither): recorded at the kernel's start and end by its own dispatch packet, instead of two
 // hipEventRecord packets around it (the fused launch, where the kernel is all the events span)
+// The tile-skip kernel exists for the widths pgpu_rd_skip_ok names; the runtime plans a skip for no other launch.
 template <int M, int PK>
-static void rd_launch(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+static hipError_t rd_launch(const DevParams& p, int grid, size_t dyn_smem, hipStream_t st, hipEvent_t ev0,
+                            hipEvent_t ev1) {
   const dim3 g(grid), b(PGPU_DIRECT_THREADS);
-#define RD_GO(PL, K)                                                                                       \
-  do {                                                                                                     \
-    if (ev0) hipExtLaunchKernelGGL((query_kernel_rdirect<M, PL, K>), g, b, dyn_smem, st, ev0, ev1, 0, p);  \
-    else hipLaunchKernelGGL((query_kernel_rdirect<M, PL, K>), g, b, dyn_smem, st, p);                      \
+  if (p.rd_skip && !pgpu_rd_skip_ok(p.rd_planes, PK)) return hipErrorInvalidValue;
+#define RD_GO_K(KERNEL, ...)                                                                  \
+  do {                                                                                        \
+    if (ev0) hipExtLaunchKernelGGL((KERNEL<M, __VA_ARGS__>), g, b, dyn_smem, st, ev0, ev1, 0, p); \
+    else hipLaunchKernelGGL((KERNEL<M, __VA_ARGS__>), g, b, dyn_smem, st, p);                     \
+  } while (0)
+#define RD_GO(PL, K)                                            \
+  do {                                                          \
+    if constexpr (PGPU_RD_SKIP_OK(PL, K)) {                     \
+      if (p.rd_skip) RD_GO_K(query_kernel_rdirect_skip, PL);    \
+      else RD_GO_K(query_kernel_rdirect, PL, K);                \
+    } else {                                                    \
+      RD_GO_K(query_kernel_rdirect, PL, K);                     \
+    }                                                           \
   } while (0)
   if (p.rd_planes <= 8) RD_GO(8, PK);
   else if (p.rd_planes <= 10) RD_GO(10, PK);
   else if (PK > 0 || p.rd_planes <= 12) RD_GO(12, PK);
   else RD_GO(16, 0);
 #undef RD_GO
+#undef RD_GO_K
+  return hipSuccess;
 }
 template <int M, int PK>
 static hipError_t rd_attrs(size_t lds_bytes) {
@@ -5800,8 +6008,9 @@ template <int M>
       } else                                                                                                    \
         return hipErrorInvalidValue;                                                                            \
     } else if (p.direct == PGPU_KV_RDIRECT) {                                                                   \
-      if (p.rd_pfx) rd_launch<M, PGPU_PFX_PLANES>(p, grid, dyn_smem, st, ev0, ev1);                             \
-      else rd_launch<M, 0>(p, grid, dyn_smem, st, ev0, ev1);                                                    \
+      const hipError_t re = p.rd_pfx ? rd_launch<M, PGPU_PFX_PLANES>(p, grid, dyn_smem, st, ev0, ev1)           \
+                                     : rd_launch<M, 0>(p, grid, dyn_smem, st, ev0, ev1);                        \
+      if (re != hipSuccess) return re;                                                                          \
     } else                                                                                                      \
       hipLaunchKernelGGL((query_kernel_direct<M>), dim3(grid), dim3(PGPU_DIRECT_THREADS), dyn_smem, st, p);     \
     return hipGetLastError();                                                                                   \

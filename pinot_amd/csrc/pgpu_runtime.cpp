@@ -67,6 +67,9 @@ hipError_t pgpu_gdict_sort_unique(const void* vals, int32_t dtype, int64_t n, ui
                                   uint64_t* uniq, uint32_t* d_card, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t pgpu_gdict_encode(const uint64_t* keys, int64_t n, const uint64_t* uniq, int32_t card, int32_t dtype,
                              int bits, void* dict, uint32_t* ids, uint32_t* words, int64_t nwords, hipStream_t st);
+// tile presence rows of a bit-sliced column (pgpu_presence.hip)
+hipError_t pgpu_launch_presence_build(const uint32_t* sliced, int bits, int32_t num_docs, uint32_t* rows, int max_wgs,
+                                      hipStream_t st);
 // fold of a group table over its last group column (pgpu_fold.hip)
 hipError_t pgpu_launch_fold(const int64_t* in, uint64_t N, int32_t nsec, const int32_t* ops, bool hash, uint64_t inner,
                             int64_t* out, int num_cus, hipStream_t st);
@@ -387,6 +390,8 @@ struct pgpu_context {
   EvSlot evring[kEvRing];
   uint64_t submit_seq = 0, last_fused_seq = 0;
   hipStream_t cstream = nullptr;  // pgpu_query_cancel: writes cancel words while the query streams are busy
+  hipStream_t bstream = nullptr;  // presence-row builds (enqueue_presence_builds): never a query stream, so no build
+                                  // sits between a query's events and no query is ordered behind one
   // workspace buffers grow from this pool in stream order (DevMem::ensure(bytes, pool, stream)); it never returns
   // memory to the device on its own (release threshold = max), so no query-path allocation reaches the driver
   // twice.  nullptr when the device has no memory pools: growth then falls back to hipMalloc / hipFree.
@@ -402,6 +407,7 @@ struct pgpu_context {
     if (qstream) (void)hipStreamDestroy(qstream);
     if (qstream2) (void)hipStreamDestroy(qstream2);
     if (cstream) (void)hipStreamDestroy(cstream);
+    if (bstream) (void)hipStreamDestroy(bstream);
     for (EvSlot& s : evring) {
       if (s.ev0) (void)hipEventDestroy(s.ev0);
       if (s.ev1) (void)hipEventDestroy(s.ev1);
@@ -421,6 +427,29 @@ struct pgpu_buffer {
 
 namespace {
 
+// Presence rows of one column (pgpu_presence.hip), built on use.  Sealed segments are shared between threads: the
+// counters and the state are atomics, `mu` serialises the one build and the polls of its event, and planners read
+// `rows` only after they have seen kReady (stored with release order behind the pointer).
+struct PresenceState {
+  enum : int { kNone = 0, kBuilding = 1, kReady = 2, kDeclined = 3 };
+  std::atomic<int> state{kNone};
+  std::atomic<int> wanted{0};  // submits whose plan would have skipped with the rows present
+  std::mutex mu;
+  DevMem rows;
+  // what the build reads, set at seal: the state outlives its segment while a query handle still holds a build to
+  // start (`released`: the segment is gone, nothing is built)
+  pgpu_context* ctx = nullptr;
+  const uint32_t* sliced = nullptr;
+  int32_t bits = 0, num_docs = 0;
+  bool released = false;
+  int32_t wpr = 0;             // words per row
+  uint64_t reserved = 0;       // bytes held of the context's derived budget
+  hipEvent_t built = nullptr;  // recorded behind the build
+  ~PresenceState() {
+    if (built) (void)hipEventDestroy(built);
+  }
+};
+
 struct HostColumn {
   int32_t kind = PGPU_COL_NONE;
   int32_t bits = 0;
@@ -433,6 +462,7 @@ struct HostColumn {
   DevMem sliced;                       // bit-sliced copy of fwd (built at seal; PGPU_NO_SLICE=1 skips it)
   DevMem vsliced;                      // bit planes of the docs' values - vmin (INT / LONG dictionaries, <= 32 bits;
                                        // built at seal; PGPU_NO_VSLICE=1 skips it)
+  std::shared_ptr<PresenceState> presence;  // made at seal beside `sliced` (eligible for presence rows), else null
   int64_t vmin = 0;
   int32_t vbits = 0;
   uint64_t fwd_bytes = 0, dict_bytes = 0, inv_bytes = 0;
@@ -486,6 +516,8 @@ struct pgpu_query {
   bool small = false;
   bool eager = false;  // compacted on the device at submit (enqueue_compact): collect only copies the rows out
   bool eager_ordered = false;  // ... restricted to the best groups by the order given at submit
+  // presence rows this submit reached the trigger of: started when the query is collected (enqueue_presence_builds)
+  std::vector<std::shared_ptr<PresenceState>> presence_builds;
   // HASH mode: tracked segments (query segment index) whose distinct keys are checked against the limit
   std::vector<int32_t> tracked;
   std::vector<uint8_t> tracked_map;  // per tracked segment: its holder is map-based (keys past the limit dropped)
@@ -1186,6 +1218,66 @@ bool reserve_derived(pgpu_context* ctx, uint64_t bytes) {
   return true;
 }
 
+// PGPU_PRESENCE_AFTER: the wanting submit that enqueues a column's presence rows (default 2; 0: built inside seal;
+// negative: never built, never used).  Read per call: tests.
+int presence_after() {
+  const char* v = getenv("PGPU_PRESENCE_AFTER");
+  if (!v || !*v) return 2;
+  char* end = nullptr;
+  const long x = strtol(v, &end, 10);
+  return end != v && *end == '\0' ? (int)std::max(-1l, std::min(x, 1l << 30)) : 2;
+}
+
+// Start the build of a column's presence rows on `st` (kNone -> kBuilding, or kDeclined when the budget or the device
+// has no room: the column is then never asked again).  ps.mu held.
+// max_wgs > 0: the build's grid at most (a build beside queries leaves them most of the CUs).
+void presence_start(PresenceState& ps, hipStream_t st, int max_wgs) {
+  if (ps.state.load() != PresenceState::kNone || ps.released) return;
+  const int64_t ntiles = ((int64_t)ps.num_docs + PGPU_WT - 1) / PGPU_WT;
+  const int64_t wpr = (ntiles + 31) / 32;
+  const uint64_t bytes = (uint64_t)PGPU_PRESENCE_ROWS * (uint64_t)wpr * 4;
+  bool ok = ps.num_docs > 0 && reserve_derived(ps.ctx, bytes);
+  if (ok) {
+    ps.reserved = bytes;
+    ok = ps.rows.alloc(bytes) == hipSuccess &&
+         (ps.built || hipEventCreateWithFlags(&ps.built, hipEventDisableTiming) == hipSuccess) &&
+         pgpu_launch_presence_build(ps.sliced, ps.bits, ps.num_docs, (uint32_t*)ps.rows.p, max_wgs, st) == hipSuccess &&
+         hipEventRecord(ps.built, st) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      // (a build that was enqueued and whose event was not: it ends before the rows are freed)
+      (void)hipStreamSynchronize(st);
+      ps.rows.reset();
+      ps.ctx->derived_bytes -= bytes;
+      ps.reserved = 0;
+    }
+  }
+  if (ok) ps.wpr = (int32_t)wpr;
+  ps.state.store(ok ? PresenceState::kBuilding : PresenceState::kDeclined, std::memory_order_release);
+}
+
+// The column's finished presence rows, or nullptr.  Never waits: a build in flight is asked once whether it is done.
+const uint32_t* presence_ready(const HostColumn& c, int32_t* wpr) {
+  PresenceState* ps = c.presence.get();
+  if (!ps) return nullptr;
+  int st = ps->state.load(std::memory_order_acquire);
+  if (st == PresenceState::kBuilding) {
+    std::lock_guard<std::mutex> lk(ps->mu);
+    st = ps->state.load(std::memory_order_acquire);
+    if (st == PresenceState::kBuilding) {
+      if (hipEventQuery(ps->built) == hipSuccess) {
+        ps->state.store(PresenceState::kReady, std::memory_order_release);
+        st = PresenceState::kReady;
+      } else {
+        (void)hipGetLastError();  // ("not ready" is no error of the launches that follow)
+      }
+    }
+  }
+  if (st != PresenceState::kReady) return nullptr;
+  *wpr = ps->wpr;
+  return (const uint32_t*)ps->rows.p;
+}
+
 int seal_column(pgpu_segment* seg, size_t i) {
   static const bool no_slice = env_flag("PGPU_NO_SLICE");
   HostColumn& c = seg->cols[i];
@@ -1202,6 +1294,19 @@ int seal_column(pgpu_segment* seg, size_t i) {
     }
     HIP_TRY(hipMemset(c.sliced.p, 0, c.sliced.n));
     HIP_TRY(pgpu_launch_bitslice((const uint32_t*)c.fwd.p, (uint32_t*)c.sliced.p, c.bits, ntiles, nullptr));
+  }
+  // presence rows: a column with a bit-sliced copy may get them, on use (pack_and_plan) or, with
+  // PGPU_PRESENCE_AFTER=0, here (pgpu_segment_seal synchronises behind the build)
+  if (c.sliced.p && c.bits >= 1 && c.bits <= 31 && !c.presence) {
+    c.presence.reset(new PresenceState());
+    c.presence->ctx = seg->ctx;
+    c.presence->sliced = (const uint32_t*)c.sliced.p;
+    c.presence->bits = c.bits;
+    c.presence->num_docs = seg->num_docs;
+    if (presence_after() == 0) {
+      std::lock_guard<std::mutex> lk(c.presence->mu);
+      presence_start(*c.presence, nullptr, 0);
+    }
   }
   // value planes (bit-sliced index of the values): SUM is then sum_k 2^k popcount(plane_k & matched) per tile and
   // MIN / MAX an MSB-first selection -- no per-doc id extraction, no dictionary gather (PGPU_AM_SLICED)
@@ -1400,9 +1505,13 @@ int pgpu_segment_device_bytes_ex(const pgpu_segment* seg, pgpu_segment_bytes* ou
     out->inverted += c.inv_dir.n + c.inv_ct.n + c.inv_data.n;
     out->sliced += c.sliced.n;
     out->value_planes += c.vsliced.n;
+    if (c.presence && c.presence->state.load(std::memory_order_acquire) != PresenceState::kNone) {
+      std::lock_guard<std::mutex> lk(c.presence->mu);  // (a build being started on another thread)
+      out->presence += c.presence->reserved;
+    }
   }
   out->total = out->forward + out->dictionary + out->sorted + out->inverted + out->multi_value + out->sliced +
-               out->value_planes;
+               out->value_planes + out->presence;
   return PGPU_OK;
 }
 
@@ -1432,7 +1541,18 @@ int pgpu_segment_release(pgpu_segment* seg) {
   if (!seg) return PGPU_OK;
   (void)hipSetDevice(seg->ctx->device);
   uint64_t derived = 0;
-  for (const HostColumn& c : seg->cols) derived += c.sliced.n + c.vsliced.n;
+  for (const HostColumn& c : seg->cols) {
+    derived += c.sliced.n + c.vsliced.n;
+    if (PresenceState* ps = c.presence.get()) {
+      std::lock_guard<std::mutex> lk(ps->mu);
+      // a build in flight reads the bit-sliced copy and writes the rows: it ends before either is freed
+      if (ps->state.load() == PresenceState::kBuilding) (void)hipEventSynchronize(ps->built);
+      derived += ps->reserved;
+      ps->reserved = 0;
+      ps->rows.reset();
+      ps->released = true;  // (a query handle may still hold the state with a build to start: it starts none)
+    }
+  }
   seg->ctx->derived_bytes -= derived;
   delete seg;
   return PGPU_OK;
@@ -3135,6 +3255,9 @@ struct LaunchPlan {
   int slice_shift = 0, ldict = 0;
   uint32_t pdict_n = 0;
   const HostColumn* for_h = nullptr;  // ldict 2: the column whose frame-of-reference image phase 2 reads
+  // presence rows this submit has reached the trigger of (plan_presence): handed to the query's handle, and
+  // started when it is collected (enqueue_presence_builds)
+  std::vector<std::shared_ptr<PresenceState>> presence_builds;
 };
 
 // PGPU_DIRECT_WGS: workgroups per CU of the self-loading kernels (0: the variant's own choice)
@@ -3736,10 +3859,21 @@ void try_pscan(int num_cus, const pgpu_query_desc* q, const pgpu_table_layout& L
   }
 }
 
+// A skipping query (plan_presence): the first skipping segment's column and id count, its modelled keep share
+struct SkipInfo {
+  bool on = false;
+  int col = -1, ids = 0;
+  double keep = 1.0;
+};
+
 // PGPU_PLAN_TRACE=1: the kernel chosen and the plan of each segment, on stderr
-void trace_plan(const Packer& pk, const DevParams& p, const LaunchPlan& pl, const LeadInfo& li) {
-  char lead[96] = "";  // a switched query only: lead column, planes, modelled bytes today -> lead
-  if (li.switched) snprintf(lead, sizeof(lead), " lead col %d P %d bytes %.0f->%.0f", li.col, li.P, li.today, li.lead);
+void trace_plan(const Packer& pk, const DevParams& p, const LaunchPlan& pl, const LeadInfo& li, const SkipInfo& si) {
+  char lead[160] = "";  // a switched query only: lead column, planes, modelled bytes today -> lead; a skipping one: skip
+  int ln = 0;
+  if (li.switched)
+    ln = snprintf(lead, sizeof(lead), " lead col %d P %d bytes %.0f->%.0f", li.col, li.P, li.today, li.lead);
+  if (si.on && ln >= 0 && ln < (int)sizeof(lead))
+    snprintf(lead + ln, sizeof(lead) - ln, " skip col %d ids %d keep %.4f", si.col, si.ids, si.keep);
   fprintf(stderr, "[pgpu plan] mode %d dense %d direct %d pscan %d grid %d dyn %zu tiles %d units %d invx %zu "
           "rd_planes %d rd_pfx %d rs_vplanes %d dslots %d min_instrs %d ring_slots %d inflight %d rk_ids %d "
           "rk_leaves %d pscan_kb %d pscan_vb %d pshift %d nparts %llu ldict %d rw %d rec_idbits %d nwaves %d%s\n",
@@ -3782,6 +3916,108 @@ int plan_launch(int num_cus, const pgpu_query_desc* q, const pgpu_table_layout& 
   return PGPU_OK;
 }
 
+// ---- register-direct tile skip (pgpu_presence_model in pinot_gpu.h; plan_presence plans with these functions) -----
+// Share of a column's tiles its presence rows keep for n point ids: the tiles that hold one of them, plus the Bloom
+// filter's false positives at d distinct ids per tile.
+double presence_keep(int card, int n) {
+  const double c = std::max(1, card), d = std::min((double)PGPU_WT, c);
+  const double hold = 1.0 - std::pow(1.0 - 1.0 / c, (double)PGPU_WT);
+  const double fpr = std::pow(1.0 - std::exp(-(double)PGPU_PRESENCE_PROBES * d / PGPU_PRESENCE_ROWS), (double)PGPU_PRESENCE_PROBES);
+  return std::min(1.0, n * hold + n * fpr);
+}
+// Bytes one segment saves: the skipped tiles' planes less the row slices every wave's probe reads once
+double presence_saved(double keep, int n, int64_t tiles, double bytes_per_tile) {
+  const int64_t wpr = (tiles + 31) / 32;
+  return (double)tiles * (1.0 - keep) * bytes_per_tile - 4.0 * PGPU_PRESENCE_PROBES * n * (double)wpr;
+}
+
+// A segment's skip child: the child of its top-level AND (or its whole filter) that is one non-negated SCAN node
+// matching at most PGPU_SLICE_RANGES single dict ids of a column eligible for presence rows, with the smallest
+// modelled keep share.  Independent of which leaf is streamed.
+struct SkipChoice {
+  const HostColumn* h = nullptr;
+  int col = -1, n = 0;
+  uint32_t ids[PGPU_SLICE_RANGES] = {};
+  double keep = 1.0;
+};
+bool skip_choice(const SegView& v, SkipChoice* out) {
+  ChildSplit cs;
+  if (!split_children(v, cs)) return false;
+  for (size_t k = 0; k < cs.kids.size(); ++k) {
+    std::vector<std::pair<uint64_t, uint64_t>> runs;
+    if (!scan_runs(v, cs.kids[k], runs) || runs.empty() || (int)runs.size() > PGPU_SLICE_RANGES) continue;
+    bool points = true;
+    for (auto& r : runs) points = points && r.second == r.first + 1;
+    if (!points) continue;
+    const int qc = v.nd[cs.kids[k].first].column;
+    const HostColumn* h = v.host(qc);
+    if (!h->presence || h->presence->state.load(std::memory_order_acquire) == PresenceState::kDeclined) continue;
+    const double keep = presence_keep(v.dev(qc)->card, (int)runs.size());
+    if (out->h && keep >= out->keep) continue;
+    out->h = h;
+    out->col = qc;
+    out->n = (int)runs.size();
+    for (int i = 0; i < out->n; ++i) out->ids[i] = (uint32_t)runs[i].first;
+    out->keep = keep;
+  }
+  return out->h != nullptr;
+}
+
+// The launch's tile skip, planned behind plan_launch (the kernel is known only then) and beside the lead decision:
+// which segments would skip with their rows present ("wanted": they count the submit and may trigger the build),
+// and which do skip, their rows being there (DevSeg::skip_*, DevParams::rd_skip).  No HIP call but hipEventQuery.
+void plan_presence(const pgpu_query_desc* q, Packer& pk, DevParams& p, LaunchPlan& pl, SkipInfo* si) {
+  const int after = presence_after();
+  const int64_t thr = pgpu_presence_switch_bytes();
+  if (p.direct != PGPU_KV_RDIRECT || (q->flags & PGPU_Q_EXACT_FILTER_STATS) || after < 0 || thr < 0) return;
+  if (!pgpu_rd_skip_ok(p.rd_planes, p.rd_pfx)) return;  // (launches the skip kernel is not built for)
+  const int nseg = (int)pk.segs.size();
+  std::vector<SkipChoice> ch((size_t)nseg);
+  std::vector<double> saved((size_t)nseg, 0.0);
+  double want = 0;
+  for (int s = 0; s < nseg; ++s) {
+    const pgpu_segment_plan& sp = q->segments[s];
+    const DevSeg& ds = pk.segs[s];
+    if (ds.ntiles <= 0 || ds.nstage < 1) continue;
+    SegView v{q, &sp, sp.segment, sp.filter, sp.num_filter_nodes};
+    if (!skip_choice(v, &ch[s])) continue;
+    const DevColumn& lc = pk.cols[ds.col_begin + ds.stage_col[0]];
+    const double bpt = 256.0 * (lc.bits - ds.f_plane0 + p.rd_pfx);
+    saved[s] = presence_saved(ch[s].keep, ch[s].n, ds.ntiles, bpt);
+    if (saved[s] > 0) want += saved[s];
+    else ch[s].h = nullptr;
+  }
+  if (!pgpu_lead_switch(want, thr)) return;
+  double have = 0;
+  std::vector<const uint32_t*> rows((size_t)nseg, nullptr);
+  std::vector<int32_t> wpr((size_t)nseg, 0);
+  for (int s = 0; s < nseg; ++s) {
+    if (!ch[s].h) continue;
+    PresenceState* ps = ch[s].h->presence.get();
+    if (ps->state.load(std::memory_order_acquire) == PresenceState::kNone && ps->wanted.fetch_add(1) + 1 >= after)
+      pl.presence_builds.push_back(ch[s].h->presence);
+    rows[s] = presence_ready(*ch[s].h, &wpr[s]);
+    if (rows[s]) have += saved[s];
+  }
+  if (!pgpu_lead_switch(have, thr)) return;
+  for (int s = 0; s < nseg; ++s) {
+    if (!rows[s]) continue;
+    DevSeg& ds = pk.segs[s];
+    ds.skip_rows = rows[s];
+    ds.skip_wpr = wpr[s];
+    ds.skip_n = ch[s].n;
+    for (int i = 0; i < ch[s].n; ++i)
+      for (int j = 0; j < PGPU_PRESENCE_PROBES; ++j) ds.skip_row[i][j] = (uint16_t)pgpu_presence_row_of(ch[s].ids[i], j);
+    if (!si->on) si->col = ch[s].col, si->ids = ch[s].n, si->keep = ch[s].keep;
+    si->on = true;
+  }
+  // the keep bits' chunk: a wave's 64 lanes hold one row word each; PGPU_PRESENCE_CHUNK_WORDS (read per plan) makes
+  // it shorter, so that tests reach a range's second chunk at their sizes
+  const char* cwe = getenv("PGPU_PRESENCE_CHUNK_WORDS");
+  const int cw = cwe && *cwe ? atoi(cwe) : 64;
+  p.rd_skip = std::min(64, std::max(1, cw));
+}
+
 // pack_query and plan_launch.  A lead-leaf switch (LeadInfo) is planned for query_kernel_rdirect only: when the
 // launch does not end on it (another condition of try_rdirect fails, PGPU_NO_RDIRECT, the LDS limit), or the lead
 // leaf did not pack as one staged SCAN (kLeadRetry), the query is packed again in query order, so that it runs
@@ -3804,7 +4040,9 @@ int pack_and_plan(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_
     if (rc) return rc;
     if (!li.switched || p.direct == PGPU_KV_RDIRECT) break;
   }
-  if (plan_trace_on()) trace_plan(pk, p, pl, li);
+  SkipInfo si;
+  plan_presence(q, pk, p, pl, &si);
+  if (plan_trace_on()) trace_plan(pk, p, pl, li, si);
   return PGPU_OK;
 }
 
@@ -4441,6 +4679,30 @@ int32_t pgpu_lead_switch(double saved_bytes, int64_t threshold_bytes) {
   return threshold_bytes >= 0 && saved_bytes > 0 && saved_bytes >= (double)threshold_bytes;
 }
 
+void pgpu_presence_rows(int32_t id, uint16_t out[4]) {
+  for (int j = 0; j < PGPU_PRESENCE_PROBES; ++j) out[j] = (uint16_t)pgpu_presence_row_of((uint32_t)id, j);
+}
+
+int pgpu_presence_model(int32_t card, int32_t num_ids, int64_t tiles, double bytes_per_tile, int64_t threshold_bytes,
+                        pgpu_presence_model_out* out) {
+  if (!out) return fail(PGPU_E_INVALID, "null argument");
+  if (card < 1 || num_ids < 1 || num_ids > PGPU_SLICE_RANGES || tiles < 0 || !(bytes_per_tile >= 0))
+    return fail(PGPU_E_INVALID, "presence model: card %d, %d ids, %lld tiles", card, num_ids, (long long)tiles);
+  memset(out, 0, sizeof(*out));
+  out->keep = presence_keep(card, num_ids);
+  out->saved_bytes = presence_saved(out->keep, num_ids, tiles, bytes_per_tile);
+  out->skip = pgpu_lead_switch(out->saved_bytes, threshold_bytes);
+  return PGPU_OK;
+}
+
+int64_t pgpu_presence_switch_bytes(void) {
+  const char* v = getenv("PGPU_PRESENCE_SWITCH_BYTES");  // read per plan: tests
+  if (!v || !*v) return kLeadSwitchBytes;
+  char* end = nullptr;
+  const long long x = strtoll(v, &end, 10);
+  return end != v && *end == '\0' ? (int64_t)x : kLeadSwitchBytes;  // (a value that does not parse: the default)
+}
+
 // Every query enters the GPU here, as a sequence of phases: pack_query, drop_reference_replay, plan_launch and
 // split_reason (host only), then pick_stream, ensure_workspace, fill_arena, enqueue_fused or enqueue_split,
 // make_query_handle.
@@ -4450,6 +4712,32 @@ int32_t pgpu_lead_switch(double saved_bytes, int64_t threshold_bytes) {
 // tws (pgpu_query_submit*): the workspace whose `table` is the query's table (dev_table is not read: the table is
 // grown here, on the query's stream); with it a register-direct query with a small table runs as one launch (see
 // Workspace::ticket) and may take the workspace's spare table as its table
+// The presence-row builds a submit triggered (plan_presence), started when that query is collected after running to
+// its end (pgpu_query_wait): the build then runs beside no kernel of the query that asked for it, and a cancelled or
+// expired query -- whose kernel time callers compare with a full run's -- starts none.  On the context's build stream:
+// lowest priority, no query stream, a quarter of the CUs, so later queries are not ordered behind it and keep most
+// of the GPU; they find the rows once the event is done.  A build that cannot start (budget, allocation) only marks
+// its column declined; a segment released in between has none.
+static void enqueue_presence_builds(pgpu_context* ctx, std::vector<std::shared_ptr<PresenceState>>& builds) {
+  if (builds.empty()) return;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int least = 0, greatest = 0;
+    if (!ctx->bstream && (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
+                          hipStreamCreateWithPriority(&ctx->bstream, hipStreamNonBlocking, least) != hipSuccess)) {
+      ctx->bstream = nullptr;
+      (void)hipGetLastError();
+      builds.clear();
+      return;
+    }
+  }
+  for (const auto& ps : builds) {
+    std::lock_guard<std::mutex> lk(ps->mu);
+    presence_start(*ps, ctx->bstream, std::max(1, ctx->num_cus / 4));
+  }
+  builds.clear();
+}
+
 static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream, void* dev_table,
                        uint64_t table_bytes, int64_t* host_table, pgpu_query** out_query, bool eager = false,
                        const pgpu_topk* eager_order = nullptr, Workspace* tws = nullptr) {
@@ -4518,6 +4806,7 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
   }
   const hipEvent_t done = kernel_is_done ? pick.ev1 : ws->done;  // (= pick.done)
   pgpu_query* qq = make_query_handle(ctx, q, pk, p, pl.grid, ws, st, done, eager);
+  qq->presence_builds = std::move(pl.presence_builds);
   qq->ev0 = pick.ev0;
   qq->ev1 = pick.ev1;
   qq->seq = pick.seq;
@@ -4589,6 +4878,7 @@ int pgpu_query_wait(pgpu_query* qq, pgpu_query_stats* out_stats) {
   } else {
     HIP_TRY(hipStreamSynchronize(qq->stream));
   }
+  if (qq->stop.load() == 0) enqueue_presence_builds(qq->ctx, qq->presence_builds);
   const int64_t* s = (const int64_t*)qq->ws->h_stats.p;
   qq->stats.num_docs_scanned = s[PGPU_STAT_MATCHED];
   qq->stats.num_entries_scanned_in_filter = s[PGPU_STAT_SCANNED] + qq->mv_entries;
