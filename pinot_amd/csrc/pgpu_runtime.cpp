@@ -30,6 +30,7 @@
 #include "../../include/pinot_gpu.h"
 #include "pgpu_host.h"
 #include "pgpu_internal.h"
+#include "pgpu_segplan.h"
 
 // kernels (pgpu_kernels.hip)
 hipError_t pgpu_prepare_query_kernels(size_t lds_bytes);
@@ -272,9 +273,14 @@ struct PinnedMem {
 };
 
 // PGPU_HOST_TIMING=N: average host microseconds of the submit phases, printed to stderr every N submits
+// A second line splits "pack" (lead decision, per-segment plans; the rest of it is pack_query's own loop) and what
+// the first line's total holds outside its buckets: plan_launch, plan_presence, the query handle, and the teardown
+// (from the finished handle to the submit's return: the destructors of launch_impl's locals).
 struct HostTiming {
+  enum { kLead = 6, kSegPlan, kPlanLaunch, kPresence, kHandle, kTeardown, kBuckets };
   int every = 0, n = 0;
-  double acc[6] = {0, 0, 0, 0, 0, 0};
+  double acc[kBuckets] = {};
+  double mark = 0;  // launch_impl: the handle is made, only destructors follow
   HostTiming() {
     const char* e = getenv("PGPU_HOST_TIMING");
     every = e ? atoi(e) : 0;
@@ -282,6 +288,7 @@ struct HostTiming {
   static double us() {
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
   }
+  bool on() const { return every > 0; }
   void add(int k, double t0, double t1) {
     if (every > 0) acc[k] += t1 - t0;
   }
@@ -289,6 +296,9 @@ struct HostTiming {
     if (every <= 0 || ++n < every) return;
     fprintf(stderr, "[pgpu host] per submit (us): expr %.1f layout %.1f pack %.1f workspace %.1f launch %.1f total %.1f\n",
             acc[0] / n, acc[1] / n, acc[2] / n, acc[3] / n, acc[4] / n, acc[5] / n);
+    fprintf(stderr, "[pgpu host] of which (us): lead %.1f segplan %.1f plan_launch %.1f presence %.1f handle %.1f "
+            "teardown %.1f\n", acc[kLead] / n, acc[kSegPlan] / n, acc[kPlanLaunch] / n, acc[kPresence] / n,
+            acc[kHandle] / n, acc[kTeardown] / n);
     n = 0;
     for (double& a : acc) a = 0;
   }
@@ -1785,7 +1795,25 @@ int pgpu_kernel_geometry(pgpu_context* ctx, int32_t* out_grid, int32_t* out_tile
 // ---- plan packing ---------------------------------------------------------------------------------------------
 namespace {
 
+// The switches that are read per plan (tests change them between two submits of one process), read once at the top
+// of pack_and_plan instead of once per segment or per variant tried.  Process-lifetime switches stay `static const`
+// where they are used.
+struct PlanEnv {
+  bool progbits = false;       // PGPU_PROGBITS
+  bool always_replay = false;  // PGPU_ALWAYS_REPLAY
+  bool no_rstream = false, no_rkey = false, rkey_ids = false, no_rprog = false, no_cand = false, no_rfsm = false;
+  bool no_pscan_prefetch = false;
+  double cand_density = 0;     // PGPU_CAND_DENSITY (kCandDensity when unset)
+  int presence_chunk_words = 64;  // PGPU_PRESENCE_CHUNK_WORDS
+  int64_t lead_switch_bytes = 0, presence_switch_bytes = 0;
+  void read();
+};
+
+// Everything pack_query and plan_launch collect about one query.  One Packer per submitting thread is reused from
+// submit to submit (SubmitScratch): clear() keeps the vectors' capacity.  Nothing outside launch_impl may keep a
+// pointer into it.
 struct Packer {
+  PlanEnv env;
   std::vector<DevSeg> segs;
   std::vector<DevInstr> instrs;
   std::vector<DevColumn> cols;
@@ -1818,6 +1846,33 @@ struct Packer {
   std::vector<int32_t> invids;
   int64_t rk_ctab_records = 0;   // query_kernel_rkey: container records of every inverted leaf (id, key)
   std::vector<uint32_t> cand;    // query_kernel_cand: {segment, container index or ~0u, first doc, last doc} per unit
+
+  // Back to a fresh Packer that keeps its vectors' storage.  Every field takes its value from a default-constructed
+  // Packer, so a field added later cannot be forgotten: a scalar is reset by the assignment, and a vector not
+  // listed here is emptied by it too and merely loses its capacity.
+  void clear() {
+    Packer fresh;
+    auto keep = [](auto& mine, auto& theirs) {
+      mine.clear();
+      theirs.swap(mine);
+    };
+    keep(segs, fresh.segs);
+    keep(instrs, fresh.instrs);
+    keep(cols, fresh.cols);
+    keep(pool, fresh.pool);
+    keep(remaps, fresh.remaps);
+    keep(tracked, fresh.tracked);
+    keep(raws, fresh.raws);
+    keep(rawvals, fresh.rawvals);
+    keep(bits_instrs, fresh.bits_instrs);
+    keep(mvs, fresh.mvs);
+    keep(mvsets, fresh.mvsets);
+    keep(invx, fresh.invx);
+    keep(jobs, fresh.jobs);
+    keep(invids, fresh.invids);
+    keep(cand, fresh.cand);
+    *this = std::move(fresh);
+  }
 };
 
 // Inverted leaves are expanded into doc bitmaps while their words stay within this budget (per query); the rest
@@ -1972,17 +2027,21 @@ int convert_filter(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const 
     int slot;
     int care;  // care slot of this frame's children
     int outer_care;
-    std::vector<int> patch;  // AND_CHILD instructions to patch with the AND_END index
+    // AND_CHILD instructions to patch with the AND_END index: the last one's index (-1: none), each holding its
+    // predecessor's in `jump` until the AND_END is emitted
+    int patch = -1;
   };
-  std::vector<Frame> st;
+  // (open frames: inline up to the slot limit, on the heap beyond it -- a chain of NOTs takes frames but no slots)
+  segplan::SmallVec<Frame, segplan::kNestCap> st;
   const int base = (int)pk.instrs.size();
   int cur = 0;     // slot the next node writes
   int care = -1;   // care slot of the next node
-  auto emit = [&](DevInstr in) {
-    in.stage_off = -1;
-    if (in.pred != 2 && in.op != PGPU_I_SORTED)  // LIST ids and SORTED inline ranges keep theirs
-      for (int k = 0; k < 8; ++k) in.ids[k] = 0xFFFFFFFFu;
+  auto emit = [&](const DevInstr& in) {
     pk.instrs.push_back(in);
+    DevInstr& d = pk.instrs.back();
+    d.stage_off = -1;
+    if (d.pred != 2 && d.op != PGPU_I_SORTED)  // LIST ids and SORTED inline ranges keep theirs
+      for (int k = 0; k < 8; ++k) d.ids[k] = 0xFFFFFFFFu;
     return (int)pk.instrs.size() - 1 - base;
   };
   auto close_nots = [&]() {
@@ -2211,7 +2270,10 @@ int convert_filter(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const 
         in.src = st.back().slot + 1;
         in.care = st.back().outer_care;
         const int idx = emit(in);
-        if (is_and) st.back().patch.push_back(idx);
+        if (is_and) {
+          pk.instrs[base + idx].jump = st.back().patch;
+          st.back().patch = idx;
+        }
         cur = st.back().slot + 1;
         care = st.back().care;
         break;
@@ -2223,7 +2285,11 @@ int convert_filter(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const 
         in.op = is_and ? PGPU_I_AND_END : PGPU_I_OR_END;
         in.dst = st.back().slot;
         const int idx = emit(in);
-        for (int p : st.back().patch) pk.instrs[base + p].jump = idx;
+        for (int p = st.back().patch; p >= 0;) {
+          const int prev = pk.instrs[base + p].jump;
+          pk.instrs[base + p].jump = idx;
+          p = prev;
+        }
         cur = st.back().slot;
         care = st.back().outer_care;
         st.pop_back();
@@ -2259,95 +2325,34 @@ struct SegView {
   const DevColumn* dev(int qc) const { return &seg->dev[sp->column_map[qc]]; }
 };
 
-// Walk the subtree at node i: estimated fraction of docs it keeps (uniform-id model for scans; exact bitmap and
-// sorted-range cardinalities), plus the query columns of its SCAN leaves.  Returns the index past the subtree or
-// -1 on malformed input.  Estimates only steer the staging decision; results never depend on them.
-int analyze(const SegView& v, int i, double* sel, std::vector<int>* scans) {
-  if (i < 0 || i >= v.n) return -1;
-  const pgpu_filter_node& x = v.nd[i];
-  const double nd = std::max(1, v.seg->num_docs);
-  auto valid_col = [&](int qc) {
-    return qc >= 0 && qc < v.q->num_columns && v.sp->column_map[qc] >= 0 &&
-           v.sp->column_map[qc] < (int32_t)v.seg->dev.size();
-  };
-  switch (x.op) {
-    case PGPU_F_MATCH_ALL: *sel = 1.0; return i + 1;
-    case PGPU_F_EMPTY: *sel = 0.0; return i + 1;
-    case PGPU_F_RAW_SCAN:
-    case PGPU_F_RANGE_INDEX:
-      if (!valid_col(x.column)) return -1;
-      if (v.dev(x.column)->kind == PGPU_COL_RAW) {  // a precomputed bitmap word per lane: never staged
-        *sel = 0.5;
-        return i + 1;
-      }
-      if (x.op == PGPU_F_RAW_SCAN) return -1;
-      [[fallthrough]];  // range index of a dictionary column: a dict-id range scan on the GPU
-    case PGPU_F_SCAN: {
-      if (!valid_col(x.column)) return -1;
-      if (v.dev(x.column)->kind == PGPU_COL_MV) {  // mvpred_kernel's bitmap word per lane: never staged
-        *sel = 0.5;
-        return i + 1;
-      }
-      const double card = std::max(1, v.dev(x.column)->card);
-      double s = x.pred == PGPU_PRED_RANGE ? std::max(0, x.hi - x.lo) / card : std::max(0, x.num_ids) / card;
-      s = std::min(1.0, s);
-      *sel = x.negate ? 1.0 - s : s;
-      scans->push_back(x.column);
-      return i + 1;
-    }
-    case PGPU_F_INVERTED: {
-      if (!valid_col(x.column)) return -1;
-      const HostColumn* h = v.host(x.column);
-      double docs = 0;
-      for (int k = 0; k < x.num_ids; ++k)
-        if (x.ids[k] >= 0 && x.ids[k] < (int32_t)h->inv_cards.size()) docs += h->inv_cards[x.ids[k]];
-      const double s = std::min(1.0, docs / nd);
-      *sel = x.negate ? 1.0 - s : s;
-      return i + 1;
-    }
-    case PGPU_F_SORTED: {
-      double docs = 0;
-      for (int k = 0; k < x.num_ids; ++k) docs += std::max(0, x.ids[2 * k + 1] - x.ids[2 * k] + 1);
-      const double s = std::min(1.0, docs / nd);
-      *sel = x.negate ? 1.0 - s : s;
-      return i + 1;
-    }
-    case PGPU_F_AND_BEGIN:
-    case PGPU_F_OR_BEGIN: {
-      const bool is_and = x.op == PGPU_F_AND_BEGIN;
-      double acc = 1.0;  // AND: product of selectivities; OR: product of (1 - s)
-      int j = i + 1;
-      while (j < v.n && v.nd[j].op != (is_and ? PGPU_F_AND_END : PGPU_F_OR_END)) {
-        double cs;
-        j = analyze(v, j, &cs, scans);
-        if (j < 0 || j >= v.n || v.nd[j].op != (is_and ? PGPU_F_AND_CHILD_END : PGPU_F_OR_CHILD_END)) return -1;
-        acc *= is_and ? cs : 1.0 - cs;
-        ++j;
-      }
-      if (j >= v.n) return -1;
-      *sel = is_and ? acc : 1.0 - acc;
-      return j + 1;
-    }
-    case PGPU_F_NOT: {
-      double cs;
-      const int j = analyze(v, i + 1, &cs, scans);
-      *sel = 1.0 - cs;
-      return j;
-    }
-    default:
-      return -1;
+// The analysis of a segment's filter program -- its top-level children, their selectivities, scan columns and id
+// runs, the dense / residual split, the lead model -- is pgpu_segplan.h (no HIP types: the CPU harness drives it).
+// pack_query computes one SegAnalysis per segment and submit; the planners below read it.
+static_assert(segplan::kTileDocs == PGPU_WT && segplan::kPfxPlanes == PGPU_PFX_PLANES &&
+              segplan::kSliceRanges == PGPU_SLICE_RANGES && segplan::kMaxSlots == PGPU_MAX_SLOTS &&
+              segplan::kMaxStage == PGPU_MAX_STAGE && segplan::kColFixedBit == PGPU_COL_FIXED_BIT &&
+              segplan::kColRaw == PGPU_COL_RAW && segplan::kColMv == PGPU_COL_MV, "pgpu_segplan.h limits");
+using segplan::LeadChoice;
+using segplan::SegAnalysis;
+using segplan::sector_touch;
+
+// What the analysis reads of the segment's query columns (every column map entry checked by the caller)
+void fill_col_views(const SegView& v, segplan::ColView* out) {
+  for (int c = 0; c < v.q->num_columns; ++c) {
+    const DevColumn* dc = v.dev(c);
+    const HostColumn* hc = v.host(c);
+    segplan::ColView& o = out[c];
+    o.kind = dc->kind;
+    o.bits = dc->bits;
+    o.card = dc->card;
+    o.valid = true;
+    o.sliced = dc->sliced != nullptr;
+    o.presence = hc->presence && hc->presence->state.load(std::memory_order_acquire) != PresenceState::kDeclined;
+    o.inv_cards = hc->inv_cards.data();
+    o.num_inv_cards = (int32_t)hc->inv_cards.size();
   }
 }
 
-// Fraction of a b-bit column's 32-B sectors that hold at least one doc when docs survive with density rho.
-double sector_touch(double rho, int bits) {
-  if (rho >= 1.0) return 1.0;
-  if (rho <= 0.0) return 0.0;
-  return 1.0 - std::pow(1.0 - rho, 256.0 / bits);
-}
-
-// A column is streamed (dense) when at least half of its sectors would be read anyway.
-constexpr double kDenseTouch = 0.5;
 // Aggregation columns are staged densely only when nearly every 32-B sector holds a matched doc: below that the
 // self-loading kernels' candidate gathers win (config 2, 9.4 % of docs, 16-bit metric, 79 % of sectors touched:
 // dense 2.37 ms, candidates 1.40 ms; 50 % of docs: dense 3.0 ms, candidates 3.8 ms).  PGPU_DENSE_TOUCH overrides.
@@ -2364,79 +2369,13 @@ double line_touch(double rho, int bits) {
 }
 constexpr int kMaxSlotBytes = 27 * 1024;  // keeps >= 3 ring slots next to the consumer areas
 
-// The ranges [lo, hi) of the top K bits of a `bits`-wide column's ids that the id runs [a, b) reach, merged, and the
-// share of the 2^K prefixes they cover.  False when there is none or more than PGPU_SLICE_RANGES.
-bool prefix_ranges(const std::vector<std::pair<uint64_t, uint64_t>>& runs, int bits, int K,
-                   std::vector<std::pair<uint32_t, uint32_t>>& merged, double* covered) {
-  const int sh = bits - K;
-  std::vector<std::pair<uint32_t, uint32_t>> pr;
-  for (auto& r : runs) pr.emplace_back((uint32_t)(r.first >> sh), (uint32_t)(((r.second - 1) >> sh) + 1));
-  std::sort(pr.begin(), pr.end());
-  merged.clear();
-  for (auto& r : pr) {
-    if (!merged.empty() && r.first <= merged.back().second) merged.back().second = std::max(merged.back().second, r.second);
-    else merged.push_back(r);
-  }
-  if (merged.empty() || (int)merged.size() > PGPU_SLICE_RANGES) return false;
-  *covered = 0;
-  for (auto& r : merged) *covered += r.second - r.first;
-  *covered /= (double)(1ull << K);
-  return true;
-}
-
-// Lead leaf of the register-direct kernel (pgpu_lead_model in pinot_gpu.h; plan_segment plans with this function).
-// A top-level AND streams its first child A and gathers the later ones per candidate.  When a later child B is far
-// more selective than A, streaming only the top P planes of B's column rejects 1 - 2^-P of the docs before anything
-// else is read: the survivors gather B's exact id (one 128-B line each, tools/gather_policy_bench.hip), and only
-// B's matches gather A.  Bytes per 2048-doc tile:
-//   today   = 256 bits_A + (prefix pre-filter ? 256 PGPU_PFX_PLANES + cand covered 128 : cand 128)
-//   lead(P) = 256 P + 2048 cov_P 128 + 2048 sel_B 128 (former dense scan children)
-// with cand = rho_dense 2048 candidates per tile; P = bits_B makes the lead leaf exact, B is not gathered again and
-// the middle term is absent.  P is one of query_kernel_rdirect's widths below bits_B, or bits_B itself up to 16.
-constexpr int kLeadWidths[4] = {8, 10, 12, 16};
-// A query switches when its segments together save at least this much: ~5 us at the 6.3 TB/s stream rate, one launch
-// boundary -- below it nothing can be observed, and small queries keep their plan.  PGPU_LEAD_SWITCH_BYTES overrides
-// (0: whenever cheaper, -1: never; read per plan: tests).
+// Lead leaf (segplan::lead_model): a query switches when its segments together save at least this much: ~5 us at
+// the 6.3 TB/s stream rate, one launch boundary -- below it nothing can be observed, and small queries keep their
+// plan.  PGPU_LEAD_SWITCH_BYTES overrides (0: whenever cheaper, -1: never; read per plan: tests).
 constexpr int64_t kLeadSwitchBytes = 32ll << 20;
 // plan_segment / pack_query: the lead leaf did not pack as one staged SCAN -- not an error, pack_and_plan packs the
 // query again in query order (no PGPU_E_* code: those are negative)
 constexpr int kLeadRetry = 1;
-void lead_model(int bits_a, double rho_dense, int residual_kind, int num_dense_scans, int bits_b, double sel_b,
-                const std::vector<std::pair<uint64_t, uint64_t>>& runs, pgpu_lead_model_out* out) {
-  memset(out, 0, sizeof(*out));
-  const double cand = rho_dense * PGPU_WT;
-  out->today_bytes = 256.0 * bits_a;
-  if (residual_kind == PGPU_LEAD_RESID_B) {  // plan_prefix's rule
-    const int K = PGPU_PFX_PLANES;
-    std::vector<std::pair<uint32_t, uint32_t>> m;
-    double cov = 1.0;
-    if (bits_b > K && prefix_ranges(runs, bits_b, K, m, &cov) && cand * 128.0 * (1.0 - cov) > 256.0 * K)
-      out->today_bytes += 256.0 * K + cand * cov * 128.0;
-    else
-      out->today_bytes += cand * 128.0;
-  } else if (residual_kind == PGPU_LEAD_RESID_OTHER) {
-    out->today_bytes += cand * 128.0;
-  }
-  auto consider = [&](int P) {
-    std::vector<std::pair<uint32_t, uint32_t>> m;
-    double cov;
-    if (!prefix_ranges(runs, bits_b, P, m, &cov)) return;
-    const double lead = 256.0 * P + (P < bits_b ? PGPU_WT * cov * 128.0 : 0.0) +
-                        PGPU_WT * sel_b * 128.0 * num_dense_scans;
-    // (a tie goes to the exact leaf, which gathers less than the model's line per survivor)
-    if (out->planes && (P < bits_b ? lead >= out->lead_bytes : lead > out->lead_bytes)) return;
-    out->planes = P;
-    out->lead_bytes = lead;
-    out->num_ranges = (int32_t)m.size();
-    for (int r = 0; r < PGPU_SLICE_RANGES; ++r) {
-      out->ranges[r][0] = r < (int)m.size() ? m[r].first : 0;
-      out->ranges[r][1] = r < (int)m.size() ? m[r].second : 0;
-    }
-  };
-  for (int P : kLeadWidths)
-    if (P < bits_b) consider(P);
-  if (bits_b <= 16) consider(bits_b);
-}
 
 // Prefix pre-filter for the register-direct kernel (DevSeg::pfx_*): when the residual program is one SCAN leaf on a
 // fixed-bit column with a bit-sliced copy, the top PGPU_PFX_PLANES planes of that column can be streamed beside the
@@ -2456,207 +2395,72 @@ void plan_prefix(const SegView& v, const Packer& pk, double rho_dense, DevSeg& d
   const DevColumn* dc = v.dev(in.col);
   const int K = PGPU_PFX_PLANES;
   if (!dc->sliced || dc->bits <= K || dc->bits > 31) return;
-  std::vector<std::pair<uint64_t, uint64_t>> runs;  // matching ids [a, b)
+  segplan::Run runs[segplan::kMaskRuns];  // matching ids [a, b): at most one per bit of a MASK
+  int nruns = 0;
   if (in.pred == 0) {
-    if (in.hi > in.lo) runs.emplace_back((uint64_t)(uint32_t)in.lo, (uint64_t)(uint32_t)in.hi);
+    if (in.hi > in.lo) runs[nruns++] = segplan::Run{(uint64_t)(uint32_t)in.lo, (uint64_t)(uint32_t)in.hi};
   } else if (in.pred == 2) {
     for (int k = 0; k < 8; ++k)
-      if (in.ids[k] != 0xFFFFFFFFu) runs.emplace_back((uint64_t)in.ids[k], (uint64_t)in.ids[k] + 1);
+      if (in.ids[k] != 0xFFFFFFFFu) runs[nruns++] = segplan::Run{(uint64_t)in.ids[k], (uint64_t)in.ids[k] + 1};
   } else if (in.pred == 3) {
     const uint64_t mask = (uint64_t)(uint32_t)in.lo | ((uint64_t)(uint32_t)in.hi << 32);
     for (int i = 0; i < 64; ++i)
-      if ((mask >> i) & 1u) runs.emplace_back((uint64_t)i, (uint64_t)i + 1);
+      if ((mask >> i) & 1u) runs[nruns++] = segplan::Run{(uint64_t)i, (uint64_t)i + 1};
   } else {
     return;
   }
-  std::vector<std::pair<uint32_t, uint32_t>> merged;
+  segplan::PrefixRange merged[PGPU_SLICE_RANGES];
+  int nmerged;
   double covered;
-  if (!prefix_ranges(runs, dc->bits, K, merged, &covered)) return;
+  if (!segplan::prefix_ranges(runs, nruns, dc->bits, K, merged, &nmerged, &covered)) return;
   const double cand = rho_dense * PGPU_WT;  // candidates per 2048-doc tile
   if (cand * 128.0 * (1.0 - covered) <= 256.0 * K) return;
   ds.pfx_col = in.col;
-  ds.pfx_nr = (int32_t)merged.size();
-  for (size_t r = 0; r < merged.size(); ++r) {
-    ds.pfx_rng[r][0] = merged[r].first;
-    ds.pfx_rng[r][1] = merged[r].second;
+  ds.pfx_nr = nmerged;
+  for (int r = 0; r < nmerged; ++r) {
+    ds.pfx_rng[r][0] = merged[r].lo;
+    ds.pfx_rng[r][1] = merged[r].hi;
   }
-}
-
-// The top-level AND children of a segment's filter in query order, split into the dense prefix (streamed) and the
-// residual rest (per candidate doc)
-struct ChildSplit {
-  std::vector<std::pair<int, int>> kids;  // node ranges [begin, end)
-  std::vector<double> sel;                // share of docs each child keeps (analyze)
-  std::vector<int> dense_kids, resid_kids, staged;
-  double rho = 1.0, rho_dense = 1.0;
-  bool residual = false;
-};
-bool split_children(const SegView& v, ChildSplit& cs) {
-  std::vector<std::pair<int, int>>& kids = cs.kids;
-  if (v.n > 0) {
-    double s;
-    std::vector<int> scans;
-    const int e = analyze(v, 0, &s, &scans);
-    if (e != v.n) return false;
-    if (v.nd[0].op == PGPU_F_AND_BEGIN) {
-      int j = 1;
-      while (v.nd[j].op != PGPU_F_AND_END) {
-        const int ce = analyze(v, j, &s, &scans);
-        kids.emplace_back(j, ce);
-        j = ce + 1;
-      }
-    } else {
-      kids.emplace_back(0, v.n);
-    }
-  }
-  // dense prefix of the children: every scan column of a dense child is read with >= kDenseTouch sector density
-  for (size_t k = 0; k < kids.size(); ++k) {
-    double s;
-    std::vector<int> scans;
-    analyze(v, kids[k].first, &s, &scans);
-    bool dense = !cs.residual;
-    for (int qc : scans)
-      if (dense && v.dev(qc)->kind == PGPU_COL_FIXED_BIT && sector_touch(cs.rho, v.dev(qc)->bits) < kDenseTouch)
-        dense = false;
-    if (dense) {
-      cs.dense_kids.push_back((int)k);
-      for (int qc : scans)
-        if (v.dev(qc)->kind == PGPU_COL_FIXED_BIT && std::find(cs.staged.begin(), cs.staged.end(), qc) == cs.staged.end())
-          cs.staged.push_back(qc);
-    } else {
-      cs.residual = true;
-      cs.resid_kids.push_back((int)k);
-    }
-    cs.sel.push_back(s);
-    cs.rho *= s;
-    if (dense) cs.rho_dense *= s;
-  }
-  return true;
-}
-
-// A segment's lead leaf (lead_model): child `kid` of the top-level AND, streamed as the top P planes of its column
-struct LeadChoice {
-  int kid = -1;  // -1: the segment keeps its query order
-  int col = -1, bits = 0, P = 0;
-  int nr = 0;
-  uint32_t rng[PGPU_SLICE_RANGES][2] = {};
-  double today = 0, lead = 0;  // modelled bytes per tile
-};
-
-// The matching dict ids [a, b) of a child that is one non-negated SCAN node (RANGE, or a set convert_filter turns
-// into an inline LIST or a MASK, clamped as it clamps them) on a fixed-bit column of <= 31 bits with a bit-sliced
-// copy.  False for any other child.
-bool scan_runs(const SegView& v, const std::pair<int, int>& kid, std::vector<std::pair<uint64_t, uint64_t>>& runs) {
-  if (kid.second - kid.first != 1) return false;
-  const pgpu_filter_node& x = v.nd[kid.first];
-  if (x.op != PGPU_F_SCAN || x.negate) return false;
-  const DevColumn* dc = v.dev(x.column);
-  if (dc->kind != PGPU_COL_FIXED_BIT || !dc->sliced || dc->bits < 1 || dc->bits > 31) return false;
-  if (x.pred == PGPU_PRED_RANGE) {
-    const int64_t lo = std::max(0, x.lo), hi = std::min(x.hi, dc->card);
-    if (hi > lo) runs.emplace_back((uint64_t)lo, (uint64_t)hi);
-    return true;
-  }
-  if (x.pred != PGPU_PRED_SET || !(dc->card <= 64 || x.num_ids <= 8) || x.num_ids < 0 || (x.num_ids && !x.ids))
-    return false;
-  for (int j = 0; j < x.num_ids; ++j) {
-    if (x.ids[j] < 0 || x.ids[j] >= dc->card) return false;
-    runs.emplace_back((uint64_t)x.ids[j], (uint64_t)x.ids[j] + 1);
-  }
-  return true;
-}
-
-// Bytes per tile a segment in query order reads more once its launch streams no prefix planes (DevParams::rd_pfx
-// is one figure per launch, and a segment with a lead leaf has none): what plan_prefix's rule says they save
-double prefix_loss(const SegView& v) {
-  ChildSplit cs;
-  std::vector<std::pair<uint64_t, uint64_t>> runs;
-  if (!split_children(v, cs) || cs.resid_kids.size() != 1 || !scan_runs(v, cs.kids[cs.resid_kids[0]], runs)) return 0;
-  const int bits = v.dev(v.nd[cs.kids[cs.resid_kids[0]].first].column)->bits, K = PGPU_PFX_PLANES;
-  std::vector<std::pair<uint32_t, uint32_t>> m;
-  double cov;
-  if (bits <= K || !prefix_ranges(runs, bits, K, m, &cov)) return 0;
-  return std::max(0.0, cs.rho_dense * PGPU_WT * 128.0 * (1.0 - cov) - 256.0 * K);
-}
-
-// The later child of the segment's top-level AND with the cheapest lead plan, when there is one: a single non-negated
-// SCAN leaf (RANGE, or a set that becomes an inline LIST / MASK) on a fixed-bit column with a bit-sliced copy, every
-// other child made of SCAN leaves on fixed-bit columns only (gathered per candidate doc; bitmap, index and raw leaves
-// keep their place in the dense program).  Not whether it pays: pack_query decides that for the whole query.
-bool lead_choice(const SegView& v, LeadChoice* out) {
-  if (v.n < 6 || v.nd[0].op != PGPU_F_AND_BEGIN) return false;
-  // (first, and without the analysis below: queries with index, bitmap or raw leaves pay one pass over their nodes)
-  for (int i = 0; i < v.n; ++i) {
-    const pgpu_filter_node& x = v.nd[i];
-    const bool mark = x.op == PGPU_F_AND_BEGIN || x.op == PGPU_F_AND_CHILD_END || x.op == PGPU_F_AND_END ||
-                      x.op == PGPU_F_OR_BEGIN || x.op == PGPU_F_OR_CHILD_END || x.op == PGPU_F_OR_END ||
-                      x.op == PGPU_F_NOT;
-    if (!mark && !(x.op == PGPU_F_SCAN && x.column >= 0 && x.column < v.q->num_columns &&
-                   v.dev(x.column)->kind == PGPU_COL_FIXED_BIT))
-      return false;
-  }
-  ChildSplit cs;
-  if (!split_children(v, cs) || cs.kids.size() < 2) return false;
-  int bits_a = 0;
-  for (int qc : cs.staged) bits_a += v.dev(qc)->bits;
-  for (size_t k = 1; k < cs.kids.size(); ++k) {
-    std::vector<std::pair<uint64_t, uint64_t>> runs;
-    if (!scan_runs(v, cs.kids[k], runs)) continue;
-    const pgpu_filter_node& x = v.nd[cs.kids[k].first];
-    const DevColumn* dc = v.dev(x.column);
-    const bool was_dense = std::find(cs.dense_kids.begin(), cs.dense_kids.end(), (int)k) != cs.dense_kids.end();
-    const int kind = cs.resid_kids.empty() ? PGPU_LEAD_RESID_NONE
-                     : cs.resid_kids.size() == 1 && cs.resid_kids[0] == (int)k ? PGPU_LEAD_RESID_B
-                                                                                : PGPU_LEAD_RESID_OTHER;
-    pgpu_lead_model_out m;
-    lead_model(bits_a, cs.rho_dense, kind, (int)cs.dense_kids.size() - (was_dense ? 1 : 0), dc->bits, cs.sel[k], runs, &m);
-    if (!m.planes || (out->kid >= 0 && m.lead_bytes >= out->lead)) continue;
-    out->kid = (int)k;
-    out->col = x.column;
-    out->bits = dc->bits;
-    out->P = m.planes;
-    out->nr = m.num_ranges;
-    for (int r = 0; r < PGPU_SLICE_RANGES; ++r) out->rng[r][0] = m.ranges[r][0], out->rng[r][1] = m.ranges[r][1];
-    out->today = m.today_bytes;
-    out->lead = m.lead_bytes;
-  }
-  return out->kid >= 0;
 }
 
 int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pgpu_segment* seg,
-                 const DevParams& p, Packer& pk, DevSeg& ds, const LeadChoice* lead = nullptr) {
+                 const DevParams& p, Packer& pk, DevSeg& ds, const SegAnalysis& cs,
+                 const LeadChoice* lead = nullptr) {
   SegView v{q, &sp, seg, sp.filter, sp.num_filter_nodes};
-  ChildSplit cs;
-  if (!split_children(v, cs)) return fail(PGPU_E_INVALID, "malformed filter program");
-  const std::vector<std::pair<int, int>>& kids = cs.kids;
+  if (!cs.ok) return fail(PGPU_E_INVALID, "malformed filter program");
+  const auto& kids = cs.kids;
   const double rho = cs.rho;
   double rho_dense = cs.rho_dense;
   bool residual = cs.residual;
-  std::vector<int> dense_kids = cs.dense_kids, resid_kids = cs.resid_kids, staged = cs.staged;
+  // (inline storage with the header's spill rule: no heap below the named capacities)
+  segplan::SmallVec<int, segplan::kKidsCap> dense_kids, resid_kids;
+  segplan::SmallVec<int, segplan::kStagedCap> staged;
   if (lead && lead->kid < 0) lead = nullptr;
   if (lead) {
     // the lead leaf alone is dense; residual: B exact (unless the lead leaf is), the former dense children in their
     // order, then the former residual children in theirs
-    std::vector<int> r;
-    if (lead->P < lead->bits) r.push_back(lead->kid);
-    for (int k : dense_kids)
-      if (k != lead->kid) r.push_back(k);
-    for (int k : resid_kids)
-      if (k != lead->kid) r.push_back(k);
-    dense_kids.assign(1, lead->kid);
-    resid_kids = r;
-    staged.assign(1, lead->col);
+    if (lead->P < lead->bits) resid_kids.push_back(lead->kid);
+    for (int k : cs.dense_kids)
+      if (k != lead->kid) resid_kids.push_back(k);
+    for (int k : cs.resid_kids)
+      if (k != lead->kid) resid_kids.push_back(k);
+    dense_kids.push_back(lead->kid);
+    staged.push_back(lead->col);
     residual = true;
-    rho_dense = cs.sel[lead->kid];
+    rho_dense = cs.kids[lead->kid].sel;
+  } else {
+    dense_kids.assign(cs.dense_kids);
+    resid_kids.assign(cs.resid_kids);
+    staged.assign(cs.staged);
   }
   auto add_stage = [&](int qc) {
-    if (std::find(staged.begin(), staged.end(), qc) == staged.end()) staged.push_back(qc);
+    if (!staged.contains(qc)) staged.push_back(qc);
   };
-  const size_t nfilter_stage = staged.size();
+  const int nfilter_stage = staged.size();
   // aggregation plan
-  std::vector<int> aggcols;
+  segplan::SmallVec<int, PGPU_MAX_AGGS> aggcols;
   auto add_agg = [&](int qc) {
-    if (std::find(aggcols.begin(), aggcols.end(), qc) == aggcols.end()) aggcols.push_back(qc);
+    if (!aggcols.contains(qc)) aggcols.push_back(qc);
   };
   for (int g = 0; g < q->num_group_columns; ++g) add_agg(q->group_columns[g]);
   for (int a = 0; a < q->num_aggs; ++a)
@@ -2724,30 +2528,36 @@ int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pg
     agg_mode = PGPU_AM_SPARSE;
   }
   while (!fits()) staged.pop_back();  // remaining scans read their tiles straight from HBM
-  // programs
-  auto build = [&](const std::vector<int>& idx, std::vector<pgpu_filter_node>& out) {
+  // programs: one child is its own node range; several are copied between AND marks
+  using NodeBuf = segplan::SmallVec<pgpu_filter_node, 4 * segplan::kKidsCap>;
+  auto build = [&](const segplan::SmallVec<int, segplan::kKidsCap>& idx, NodeBuf& out, int* count) {
+    if (idx.size() == 0) {
+      *count = 0;
+      return (const pgpu_filter_node*)nullptr;
+    }
+    if (idx.size() == 1) {
+      *count = kids[idx[0]].end - kids[idx[0]].begin;
+      return v.nd + kids[idx[0]].begin;
+    }
     pgpu_filter_node mark{};
-    if (idx.size() > 1) {
-      mark.op = PGPU_F_AND_BEGIN;
-      out.push_back(mark);
-    }
+    mark.op = PGPU_F_AND_BEGIN;
+    out.push_back(mark);
+    mark.op = PGPU_F_AND_CHILD_END;
     for (int k : idx) {
-      for (int i = kids[k].first; i < kids[k].second; ++i) out.push_back(v.nd[i]);
-      if (idx.size() > 1) {
-        mark.op = PGPU_F_AND_CHILD_END;
-        out.push_back(mark);
-      }
-    }
-    if (idx.size() > 1) {
-      mark.op = PGPU_F_AND_END;
+      for (int i = kids[k].begin; i < kids[k].end; ++i) out.push_back(v.nd[i]);
       out.push_back(mark);
     }
+    mark.op = PGPU_F_AND_END;
+    out.push_back(mark);
+    *count = out.size();
+    return (const pgpu_filter_node*)out.data();
   };
-  std::vector<pgpu_filter_node> dn, rn;
-  build(dense_kids, dn);
-  build(resid_kids, rn);
+  NodeBuf dbuf, rbuf;
+  int dcount, rcount;
+  const pgpu_filter_node* dn = build(dense_kids, dbuf, &dcount);
+  const pgpu_filter_node* rn = build(resid_kids, rbuf, &rcount);
   ds.prog_begin = (int32_t)pk.instrs.size();
-  int rc = convert_filter(q, sp, dn.data(), (int)dn.size(), seg, pk);
+  int rc = convert_filter(q, sp, dn, dcount, seg, pk);
   if (rc) return rc;
   ds.prog_len = (int32_t)pk.instrs.size() - ds.prog_begin;
   ds.nbits = 0;
@@ -2762,14 +2572,14 @@ int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pg
     }
   }
   ds.rprog_begin = (int32_t)pk.instrs.size();
-  rc = convert_filter(q, sp, rn.data(), (int)rn.size(), seg, pk);
+  rc = convert_filter(q, sp, rn, rcount, seg, pk);
   if (rc) return rc;
   ds.rprog_len = (int32_t)pk.instrs.size() - ds.rprog_begin;
   if (lead) ds.pfx_col = -1;  // (the lead leaf is the pre-filter)
   else plan_prefix(v, pk, rho_dense, ds);
   auto stage_index = [&](int qc) {
-    for (size_t j = 0; j < staged.size(); ++j)
-      if (staged[j] == qc) return (int)j;
+    for (int j = 0; j < staged.size(); ++j)
+      if (staged[j] == qc) return j;
     return -1;
   };
   // fast dense program: one staged SCAN leaf, or AND_BEGIN (SCAN AND_CHILD){2} AND_END, RANGE / MASK predicates
@@ -2818,53 +2628,57 @@ int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pg
     const DevInstr& in = pk.instrs[ds.prog_begin + ds.fast_ins[j]];
     const DevColumn* dc = v.dev(in.col);
     if (!dc->sliced || dc->bits < 1 || dc->bits > 31) continue;
-    if (agg_mode == PGPU_AM_DENSE && std::find(aggcols.begin(), aggcols.end(), in.col) != aggcols.end()) continue;
+    if (agg_mode == PGPU_AM_DENSE && aggcols.contains(in.col)) continue;
     if (ds.fast == 2 && pk.instrs[ds.prog_begin + ds.fast_ins[1 - j]].col == in.col) continue;
     const uint64_t top = 1ull << dc->bits;
-    std::vector<std::pair<uint32_t, uint32_t>> rng;
+    // (the runs of one bit value among 64 bits: at most 32)
+    segplan::PrefixRange rng[33], other[33];
+    int nrng = 0;
     bool neg = in.negate != 0;
     if (in.pred == 0) {
       if (in.lo < 0 || in.hi < 0 || (uint64_t)in.lo > top || (uint64_t)in.hi > top) continue;
-      rng.emplace_back((uint32_t)in.lo, (uint32_t)in.hi);
+      rng[nrng++] = segplan::PrefixRange{(uint32_t)in.lo, (uint32_t)in.hi};
     } else {
       const uint64_t mask = (uint64_t)(uint32_t)in.lo | ((uint64_t)(uint32_t)in.hi << 32);
       const int n = (int)std::min<uint64_t>(64, top);
-      auto runs = [&](bool bit) {
-        std::vector<std::pair<uint32_t, uint32_t>> out;
+      auto runs = [&](bool bit, segplan::PrefixRange* out) {
+        int c = 0;
         for (int i = 0; i < n;) {
           if (((mask >> i) & 1u) != (uint64_t)bit) { ++i; continue; }
           int e = i;
           while (e < n && ((mask >> e) & 1u) == (uint64_t)bit) ++e;
-          out.emplace_back((uint32_t)i, (uint32_t)e);
+          out[c++] = segplan::PrefixRange{(uint32_t)i, (uint32_t)e};
           i = e;
         }
-        return out;
+        return c;
       };
-      auto set = runs(true), clr = runs(false);
-      if (set.size() <= clr.size()) rng = set;
-      else { rng = clr; neg = !neg; }
-      if (rng.empty()) rng.emplace_back(0u, 0u);  // matches no id
-      if ((int)rng.size() > PGPU_SLICE_RANGES) continue;
+      const int nset = runs(true, rng), nclr = runs(false, other);
+      nrng = nset;
+      if (nset > nclr) {
+        nrng = nclr;
+        for (int r = 0; r < nclr; ++r) rng[r] = other[r];
+        neg = !neg;
+      }
+      if (nrng == 0) rng[nrng++] = segplan::PrefixRange{0u, 0u};  // matches no id
+      if (nrng > PGPU_SLICE_RANGES) continue;
     }
-    ds.f_nr[j] = (int32_t)rng.size();
+    ds.f_nr[j] = nrng;
     ds.f_sneg[j] = neg ? 1 : 0;
-    for (size_t r = 0; r < rng.size(); ++r) {
-      ds.f_rng[j][r][0] = rng[r].first;
-      ds.f_rng[j][r][1] = rng[r].second;
+    for (int r = 0; r < nrng; ++r) {
+      ds.f_rng[j][r][0] = rng[r].lo;
+      ds.f_rng[j][r][1] = rng[r].hi;
     }
     ds.stage_sliced |= 1 << stage_index(in.col);
   }
   // staging layout
-  std::vector<int> stage_offs;
   ds.nstage = (int32_t)staged.size();
   ds.stage_instrs = 0;
   int off = 0;
-  for (size_t j = 0; j < staged.size(); ++j) {
+  for (int j = 0; j < staged.size(); ++j) {
     const int b = v.dev(staged[j])->bits;
     const bool sl = (ds.stage_sliced >> j) & 1;
     ds.stage_col[j] = staged[j];
     ds.stage_off[j] = off;
-    stage_offs.push_back(off);
     off += pgpu_stage_region_bytes(b, sl);
     ds.stage_instrs += pgpu_stage_instrs(b, sl);
   }
@@ -2872,7 +2686,7 @@ int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pg
     DevInstr& in = pk.instrs[i];
     if (in.op != PGPU_I_SCAN) continue;
     const int j = stage_index(in.col);
-    if (j >= 0) in.stage_off = stage_offs[j];
+    if (j >= 0) in.stage_off = ds.stage_off[j];
   }
   int64_t tb = 0;
   for (int qc : staged) tb += 256ll * v.dev(qc)->bits;
@@ -2883,11 +2697,9 @@ int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pg
   static const bool vstage = env_flag("PGPU_VSTAGE");
   ds.nvstage = 0;
   if (agg_mode == PGPU_AM_SLICED && all_bsi && vstage) {
-    std::vector<int> vcols;
+    segplan::SmallVec<int, PGPU_MAX_AGGS> vcols;
     for (int a = 0; a < q->num_aggs; ++a)
-      if (q->aggs[a].fn != PGPU_AGG_COUNT &&
-          std::find(vcols.begin(), vcols.end(), q->aggs[a].column) == vcols.end())
-        vcols.push_back(q->aggs[a].column);
+      if (q->aggs[a].fn != PGPU_AGG_COUNT && !vcols.contains(q->aggs[a].column)) vcols.push_back(q->aggs[a].column);
     int vinstrs = 0, vbytes = 0;
     for (int qc : vcols) {
       vinstrs += (v.dev(qc)->vbits + 3) / 4;
@@ -2913,7 +2725,7 @@ int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pg
   ds.reg_col[0] = ds.reg_col[1] = -1;
   if (agg_mode == PGPU_AM_DENSE && aggcols.size() <= 2) {
     ds.nreg = (int32_t)aggcols.size();
-    for (size_t j = 0; j < aggcols.size(); ++j) ds.reg_col[j] = aggcols[j];
+    for (int j = 0; j < aggcols.size(); ++j) ds.reg_col[j] = aggcols[j];
   }
   // An index-only dense program of several leaves (bitmap / expanded-bitmap / sorted, AND / OR / NOT) is evaluated
   // once per query for all of the segment's tiles (progbits_kernel) into a match bitmap; the query kernels then
@@ -2922,8 +2734,7 @@ int plan_segment(const pgpu_query_desc* q, const pgpu_segment_plan& sp, const pg
   // Opt-in (PGPU_PROGBITS=1): measured slower on config 3 -- progbits_kernel 1.78 ms plus the query kernel's 0.92 ms
   // against 1.60 ms for the query kernel interpreting the program itself (the per-tile interpreter, not the leaf
   // loads, is the cost, and it moves with the program).
-  const char* pbe = getenv("PGPU_PROGBITS");  // read per plan: tests switch it within one process
-  const bool progbits = pbe && atoi(pbe) != 0;
+  const bool progbits = pk.env.progbits;  // (PlanEnv: read per plan, tests switch it within one process)
   ds.single_bits = 0;
   if (progbits && ds.fast == 0 && ds.rprog_len == 0 && ds.prog_len > 1 && ds.ntiles > 0) {
     int leaves = 0;
@@ -3037,8 +2848,68 @@ struct LeadInfo {
   double today = 0, lead = 0;  // modelled bytes of the whole query
 };
 
+void PlanEnv::read() {
+  progbits = env_flag("PGPU_PROGBITS");
+  always_replay = env_flag("PGPU_ALWAYS_REPLAY");
+  no_rstream = env_flag("PGPU_NO_RSTREAM");
+  no_rkey = env_flag("PGPU_NO_RKEY");
+  rkey_ids = env_flag("PGPU_RKEY_IDS");
+  no_rprog = env_flag("PGPU_NO_RPROG");
+  no_cand = env_flag("PGPU_NO_CAND");
+  no_rfsm = env_flag("PGPU_NO_RFSM");
+  no_pscan_prefetch = env_flag("PGPU_NO_PSCAN_PREFETCH");
+  const char* cd = getenv("PGPU_CAND_DENSITY");
+  cand_density = cd ? atof(cd) : kCandDensity;
+  const char* cwe = getenv("PGPU_PRESENCE_CHUNK_WORDS");
+  presence_chunk_words = cwe && *cwe ? atoi(cwe) : 64;
+  lead_switch_bytes = pgpu_lead_switch_bytes();
+  presence_switch_bytes = pgpu_presence_switch_bytes();
+}
+
+// A submit's planning scratch beside its Packer: the per-segment analyses with the column views they read, and the
+// lead choices.  One per submitting thread (thread_local, as the Packer): a submit plans from start to end on its
+// caller's thread, so two submits that overlap never share one, and the storage keeps its capacity from one submit
+// to the next.  Nothing a pgpu_query keeps points into it.
+struct PlanScratch {
+  std::vector<std::unique_ptr<SegAnalysis>> an;  // per query segment (SmallVec members: not movable)
+  std::vector<segplan::ColView> cols;            // num_segments x num_columns
+  std::vector<LeadChoice> leads;
+  std::vector<uint8_t> viewed;                   // per segment: its column views are filled
+  int ncols = 0;
+  void begin(const pgpu_query_desc* q) {
+    const size_t nseg = (size_t)std::max(0, q->num_segments);
+    ncols = std::max(0, q->num_columns);
+    while (an.size() < nseg) an.emplace_back(new SegAnalysis());
+    for (size_t s = 0; s < nseg; ++s) an[s]->done = false;
+    cols.resize(nseg * (size_t)ncols);
+    viewed.assign(nseg, 0);
+    leads.assign(nseg, LeadChoice());
+  }
+  // The segment's program over its column views, filled at their first use in this submit (the caller has checked
+  // the segment's column map)
+  segplan::ProgView view(const SegView& v, int s) {
+    segplan::ColView* c = cols.data() + (size_t)s * ncols;
+    if (!viewed[s]) {
+      fill_col_views(v, c);
+      viewed[s] = 1;
+    }
+    return segplan::ProgView{v.nd, v.n, c, ncols, v.seg->num_docs};
+  }
+  // The segment's analysis, computed at its first use in this submit
+  const SegAnalysis& analysis(const SegView& v, int s) {
+    SegAnalysis& a = *an[s];
+    if (!a.done) segplan::analyze_segment(view(v, s), a);
+    return a;
+  }
+};
+PlanScratch& plan_scratch() {
+  static thread_local PlanScratch s;
+  return s;
+}
+
 int pack_query(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_layout& L, Packer& pk, DevParams& p,
                LeadInfo* li = nullptr) {
+  PlanScratch& sc = plan_scratch();
   memset(&p, 0, sizeof(p));
   p.ncols = q->num_columns;
   p.ngcols = q->num_group_columns;
@@ -3101,9 +2972,12 @@ int pack_query(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_lay
   // lead leaf: the segments that have one switch together when the query's tiles save enough by it; a segment that
   // has none keeps its order and is charged the prefix planes it loses.  Not with exact filter statistics
   // (query_kernel_rfsm needs both leaves in full) nor multi-value group keys (ring kernel only).
-  std::vector<LeadChoice> leads((size_t)std::max(0, q->num_segments));
+  sc.begin(q);
+  std::vector<LeadChoice>& leads = sc.leads;
   if (li) li->switched = false;
-  const int64_t lead_thr = pgpu_lead_switch_bytes();
+  HostTiming& ht = host_timing();
+  const double tlead0 = ht.on() ? HostTiming::us() : 0;
+  const int64_t lead_thr = pk.env.lead_switch_bytes;
   if (li && li->allow && lead_thr >= 0 && !(q->flags & PGPU_Q_EXACT_FILTER_STATS) && !p.mv_gmask) {
     bool ok = true, any = false;
     double today = 0, lead = 0;
@@ -3119,7 +2993,10 @@ int pack_query(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_lay
       SegView v{q, &sp, seg, sp.filter, sp.num_filter_nodes};
       if (v.n == 1 && v.nd[0].op == PGPU_F_EMPTY) continue;  // no tiles
       const double nt = (double)((seg->num_docs + PGPU_WT - 1) / PGPU_WT);
-      if (!lead_choice(v, &leads[s])) continue;
+      // (the analysis only behind lead_candidate: queries with index, bitmap or raw leaves pay one pass over their
+      // nodes here)
+      const segplan::ProgView pv = sc.view(v, s);
+      if (!segplan::lead_candidate(pv) || !segplan::lead_choice(pv, sc.analysis(v, s), &leads[s])) continue;
       today += nt * leads[s].today;
       lead += nt * leads[s].lead;
       if (!any) li->col = leads[s].col, li->P = leads[s].P;
@@ -3130,12 +3007,14 @@ int pack_query(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_lay
       const pgpu_segment_plan& sp = q->segments[s];
       SegView v{q, &sp, sp.segment, sp.filter, sp.num_filter_nodes};
       if (leads[s].kid >= 0 || (v.n == 1 && v.nd[0].op == PGPU_F_EMPTY)) continue;
-      lead += (double)((sp.segment->num_docs + PGPU_WT - 1) / PGPU_WT) * prefix_loss(v);
+      lead += (double)((sp.segment->num_docs + PGPU_WT - 1) / PGPU_WT) *
+              segplan::prefix_loss(sc.view(v, s), sc.analysis(v, s));
     }
     li->switched = ok && any && pgpu_lead_switch(today - lead, lead_thr);
     li->today = today;
     li->lead = lead;
   }
+  if (ht.on()) ht.add(HostTiming::kLead, tlead0, HostTiming::us());
   const bool lead_on = li && li->switched;
   int64_t tiles = 0;
   for (int s = 0; s < q->num_segments; ++s) {
@@ -3176,7 +3055,10 @@ int pack_query(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_lay
         return fail(PGPU_E_UNSUPPORTED, "segment %d: aggregation over a multi-value column (use its row columns)", s);
       if (c.dict_type != L.agg_value_type[a]) return fail(PGPU_E_INVALID, "segment %d: agg column type differs", s);
     }
-    int rc = plan_segment(q, sp, seg, p, pk, ds, lead_on ? &leads[s] : nullptr);
+    const double tseg0 = ht.on() ? HostTiming::us() : 0;
+    const SegView sv{q, &sp, seg, sp.filter, sp.num_filter_nodes};
+    int rc = plan_segment(q, sp, seg, p, pk, ds, sc.analysis(sv, s), lead_on ? &leads[s] : nullptr);
+    if (ht.on()) ht.add(HostTiming::kSegPlan, tseg0, HostTiming::us());
     if (rc) return rc;
     // a filter folded to EMPTY (a literal absent from the dictionary under an AND, ...) matches nothing: the
     // reference's EmptyFilterOperator scans no doc, so the segment gets no tiles
@@ -3305,7 +3187,7 @@ void drop_reference_replay(const pgpu_query_desc* q, Packer& pk) {
     for (int i = 0; i < sp.num_filter_nodes && all_ref; ++i) nmv += mv_scan_column(q, sp, sp.filter[i]) != nullptr;
     all_ref = all_ref && (nmv == 0 || sp.num_filter_nodes == 1);
   }
-  if (all_ref && !env_flag("PGPU_ALWAYS_REPLAY")) {  // (per plan: tests)
+  if (all_ref && !pk.env.always_replay) {  // (per plan: tests)
     pk.leaf_words = 0;
     for (DevSeg& ds : pk.segs) ds.leaf_len = 0;
   }
@@ -3472,7 +3354,7 @@ void try_rdirect(int num_cus, const Packer& pk, DevParams& p, LaunchPlan& pl) {
 // leaves (<= 16 and <= 8 bits) with its aggregations all answered from one column's value planes (<= 24)
 void try_rstream(int num_cus, const Packer& pk, DevParams& p, LaunchPlan& pl) {
   const size_t rdyn = reg_kernel_lds(p);
-  bool rs = !env_flag("PGPU_NO_RSTREAM") && p.mode == PGPU_MODE_AGG && rdyn <= PGPU_LDS_LIMIT;  // per plan (tests)
+  bool rs = !pk.env.no_rstream && p.mode == PGPU_MODE_AGG && rdyn <= PGPU_LDS_LIMIT;  // per plan (tests)
   int vcol = -1, rs_narrow = 1, rs_vb = 1;
   for (int a = 0; a < p.nagg && rs; ++a) {
     const DevAgg& ag = p.aggs[a];
@@ -3510,7 +3392,7 @@ void try_rstream(int num_cus, const Packer& pk, DevParams& p, LaunchPlan& pl) {
 // indices and the container-table offsets are written into the segments and leaves whether or not it is taken.
 void try_rkey(int num_cus, Packer& pk, DevParams& p, LaunchPlan& pl, const int* vcols, int nv, int vbmax) {
   // (not under the exact-statistics replay: leafbits_kernel reads the inverted leaves as expanded bitmaps)
-  bool rk = !env_flag("PGPU_NO_RKEY") && !pk.invx.empty() && pk.leaf_words == 0;  // per plan (tests)
+  bool rk = !pk.env.no_rkey && !pk.invx.empty() && pk.leaf_words == 0;  // per plan (tests)
   int maxbits = 0, units = 0;
   for (DevSeg& ds : pk.segs) {
     ds.unit_begin = units;
@@ -3551,7 +3433,7 @@ void try_rkey(int num_cus, Packer& pk, DevParams& p, LaunchPlan& pl, const int* 
       const DevColumn& vc = pk.cols[ds.col_begin + vcols[c]];
       ids = vc.kind == PGPU_COL_FIXED_BIT && vc.bits == 16 && vc.dict != nullptr && vc.fwd != nullptr;
     }
-  p.rk_ids = ids && env_flag("PGPU_RKEY_IDS") ? 1 : 0;
+  p.rk_ids = ids && pk.env.rkey_ids ? 1 : 0;
   const int per_cu = (int)std::min<size_t>(nv > 1 && vbmax > 20 ? 2 : 3, PGPU_LDS_LIMIT / kdyn);
   pl.grid = stream_grid(num_cus, per_cu, units, 2);
   pl.dyn = kdyn;
@@ -3562,7 +3444,7 @@ void try_rkey(int num_cus, Packer& pk, DevParams& p, LaunchPlan& pl, const int* 
 // value planes (<= 24).  When taken, rkey is tried on top of it.
 void try_rprog(int num_cus, Packer& pk, DevParams& p, LaunchPlan& pl) {
   if (p.direct != PGPU_KV_DIRECT || p.mode != PGPU_MODE_AGG) return;
-  bool rp = !env_flag("PGPU_NO_RPROG");  // per plan (tests)
+  bool rp = !pk.env.no_rprog;  // per plan (tests)
   int vcols[2] = {-1, -1}, nv = 0, vbmax = 1;
   for (int a = 0; a < p.nagg && rp; ++a) {
     const DevAgg& ag = p.aggs[a];
@@ -3606,8 +3488,8 @@ void try_rprog(int num_cus, Packer& pk, DevParams& p, LaunchPlan& pl) {
 void try_cand(int num_cus, const pgpu_query_desc* q, Packer& pk, DevParams& p, LaunchPlan& pl) {
   pk.cand.clear();
   if (p.direct != PGPU_KV_DIRECT) return;
-  const double cand_max = getenv("PGPU_CAND_DENSITY") ? atof(getenv("PGPU_CAND_DENSITY")) : kCandDensity;
-  bool ok = !env_flag("PGPU_NO_CAND");
+  const double cand_max = pk.env.cand_density;
+  bool ok = !pk.env.no_cand;
   std::vector<uint32_t> units;  // {segment, container index (~0u: a sorted doc range), first doc, last doc}
   std::vector<int> leaves;
   for (int s = 0; s < (int)pk.segs.size() && ok; ++s) {
@@ -3692,7 +3574,7 @@ void try_cand(int num_cus, const pgpu_query_desc* q, Packer& pk, DevParams& p, L
 // with every segment an AND of two bit-sliced leaves (andfsm's two-leaf build), both leaves' planes are streamed
 // once for the query and the tile maps together (PGPU_NO_RFSM=1, read per plan: tests)
 void try_rfsm(int num_cus, const Packer& pk, DevParams& p, LaunchPlan& pl) {
-  if (p.direct != PGPU_KV_RDIRECT || !pk.fsm || !pk.fsm_s2 || p.mode == PGPU_MODE_PART || env_flag("PGPU_NO_RFSM"))
+  if (p.direct != PGPU_KV_RDIRECT || !pk.fsm || !pk.fsm_s2 || p.mode == PGPU_MODE_PART || pk.env.no_rfsm)
     return;
   int b0 = 1, b1 = 1;
   for (const DevSeg& ds : pk.segs)
@@ -3829,7 +3711,7 @@ void try_pscan(int num_cus, const pgpu_query_desc* q, const pgpu_table_layout& L
       p.pscan_wave_bytes = (int32_t)wave_bytes;
       // the widths the prefetching phase 1 is compiled for (part_scan_kernel<false, KB, VB>)
       p.pscan_kb = p.pscan_vb = 0;
-      if (!env_flag("PGPU_NO_PSCAN_PREFETCH") && p.ngcols == 1 && pl.pcol >= 0) {  // (per plan: tests)
+      if (!pk.env.no_pscan_prefetch && p.ngcols == 1 && pl.pcol >= 0) {  // (per plan: tests)
         int kb = -1, vb = -1;
         bool same = true;
         for (const DevSeg& ds : pk.segs) {
@@ -3920,10 +3802,17 @@ int plan_launch(int num_cus, const pgpu_query_desc* q, const pgpu_table_layout& 
 // Share of a column's tiles its presence rows keep for n point ids: the tiles that hold one of them, plus the Bloom
 // filter's false positives at d distinct ids per tile.
 double presence_keep(int card, int n) {
+  // (two pow and an exp: neighbouring segments of one table ask with the same cardinality, so the last answer is
+  // kept per thread -- the same double, computed once)
+  static thread_local int memo_card = -1, memo_n = -1;
+  static thread_local double memo_keep = 0;
+  if (card == memo_card && n == memo_n) return memo_keep;
   const double c = std::max(1, card), d = std::min((double)PGPU_WT, c);
   const double hold = 1.0 - std::pow(1.0 - 1.0 / c, (double)PGPU_WT);
   const double fpr = std::pow(1.0 - std::exp(-(double)PGPU_PRESENCE_PROBES * d / PGPU_PRESENCE_ROWS), (double)PGPU_PRESENCE_PROBES);
-  return std::min(1.0, n * hold + n * fpr);
+  memo_card = card;
+  memo_n = n;
+  return memo_keep = std::min(1.0, n * hold + n * fpr);
 }
 // Bytes one segment saves: the skipped tiles' planes less the row slices every wave's probe reads once
 double presence_saved(double keep, int n, int64_t tiles, double bytes_per_tile) {
@@ -3940,27 +3829,39 @@ struct SkipChoice {
   uint32_t ids[PGPU_SLICE_RANGES] = {};
   double keep = 1.0;
 };
-bool skip_choice(const SegView& v, SkipChoice* out) {
-  ChildSplit cs;
-  if (!split_children(v, cs)) return false;
-  for (size_t k = 0; k < cs.kids.size(); ++k) {
-    std::vector<std::pair<uint64_t, uint64_t>> runs;
-    if (!scan_runs(v, cs.kids[k], runs) || runs.empty() || (int)runs.size() > PGPU_SLICE_RANGES) continue;
+bool skip_choice(const SegView& v, const SegAnalysis& cs, SkipChoice* out) {
+  if (!cs.ok) return false;
+  for (const segplan::Child& kid : cs.kids) {
+    const int nruns = kid.run_end - kid.run_begin;
+    if (!kid.runs_ok || nruns == 0 || nruns > PGPU_SLICE_RANGES) continue;
+    const segplan::Run* runs = cs.runs.data() + kid.run_begin;
     bool points = true;
-    for (auto& r : runs) points = points && r.second == r.first + 1;
+    for (int i = 0; i < nruns; ++i) points = points && runs[i].b == runs[i].a + 1;
     if (!points) continue;
-    const int qc = v.nd[cs.kids[k].first].column;
+    const int qc = v.nd[kid.begin].column;
     const HostColumn* h = v.host(qc);
     if (!h->presence || h->presence->state.load(std::memory_order_acquire) == PresenceState::kDeclined) continue;
-    const double keep = presence_keep(v.dev(qc)->card, (int)runs.size());
+    const double keep = presence_keep(v.dev(qc)->card, nruns);
     if (out->h && keep >= out->keep) continue;
     out->h = h;
     out->col = qc;
-    out->n = (int)runs.size();
-    for (int i = 0; i < out->n; ++i) out->ids[i] = (uint32_t)runs[i].first;
+    out->n = nruns;
+    for (int i = 0; i < out->n; ++i) out->ids[i] = (uint32_t)runs[i].a;
     out->keep = keep;
   }
   return out->h != nullptr;
+}
+
+// plan_presence's per-segment lists, kept from submit to submit like PlanScratch
+struct PresenceScratch {
+  std::vector<SkipChoice> ch;
+  std::vector<double> saved;
+  std::vector<const uint32_t*> rows;
+  std::vector<int32_t> wpr;
+};
+PresenceScratch& presence_scratch() {
+  static thread_local PresenceScratch s;
+  return s;
 }
 
 // The launch's tile skip, planned behind plan_launch (the kernel is known only then) and beside the lead decision:
@@ -3968,19 +3869,23 @@ bool skip_choice(const SegView& v, SkipChoice* out) {
 // and which do skip, their rows being there (DevSeg::skip_*, DevParams::rd_skip).  No HIP call but hipEventQuery.
 void plan_presence(const pgpu_query_desc* q, Packer& pk, DevParams& p, LaunchPlan& pl, SkipInfo* si) {
   const int after = presence_after();
-  const int64_t thr = pgpu_presence_switch_bytes();
+  const int64_t thr = pk.env.presence_switch_bytes;
   if (p.direct != PGPU_KV_RDIRECT || (q->flags & PGPU_Q_EXACT_FILTER_STATS) || after < 0 || thr < 0) return;
   if (!pgpu_rd_skip_ok(p.rd_planes, p.rd_pfx)) return;  // (launches the skip kernel is not built for)
   const int nseg = (int)pk.segs.size();
-  std::vector<SkipChoice> ch((size_t)nseg);
-  std::vector<double> saved((size_t)nseg, 0.0);
+  PlanScratch& sc = plan_scratch();  // (pack_query has analysed every segment of this submit)
+  PresenceScratch& ps = presence_scratch();
+  std::vector<SkipChoice>& ch = ps.ch;
+  std::vector<double>& saved = ps.saved;
+  ch.assign((size_t)nseg, SkipChoice());
+  saved.assign((size_t)nseg, 0.0);
   double want = 0;
   for (int s = 0; s < nseg; ++s) {
     const pgpu_segment_plan& sp = q->segments[s];
     const DevSeg& ds = pk.segs[s];
     if (ds.ntiles <= 0 || ds.nstage < 1) continue;
     SegView v{q, &sp, sp.segment, sp.filter, sp.num_filter_nodes};
-    if (!skip_choice(v, &ch[s])) continue;
+    if (!skip_choice(v, sc.analysis(v, s), &ch[s])) continue;
     const DevColumn& lc = pk.cols[ds.col_begin + ds.stage_col[0]];
     const double bpt = 256.0 * (lc.bits - ds.f_plane0 + p.rd_pfx);
     saved[s] = presence_saved(ch[s].keep, ch[s].n, ds.ntiles, bpt);
@@ -3989,12 +3894,14 @@ void plan_presence(const pgpu_query_desc* q, Packer& pk, DevParams& p, LaunchPla
   }
   if (!pgpu_lead_switch(want, thr)) return;
   double have = 0;
-  std::vector<const uint32_t*> rows((size_t)nseg, nullptr);
-  std::vector<int32_t> wpr((size_t)nseg, 0);
+  std::vector<const uint32_t*>& rows = ps.rows;
+  std::vector<int32_t>& wpr = ps.wpr;
+  rows.assign((size_t)nseg, nullptr);
+  wpr.assign((size_t)nseg, 0);
   for (int s = 0; s < nseg; ++s) {
     if (!ch[s].h) continue;
-    PresenceState* ps = ch[s].h->presence.get();
-    if (ps->state.load(std::memory_order_acquire) == PresenceState::kNone && ps->wanted.fetch_add(1) + 1 >= after)
+    PresenceState* st = ch[s].h->presence.get();
+    if (st->state.load(std::memory_order_acquire) == PresenceState::kNone && st->wanted.fetch_add(1) + 1 >= after)
       pl.presence_builds.push_back(ch[s].h->presence);
     rows[s] = presence_ready(*ch[s].h, &wpr[s]);
     if (rows[s]) have += saved[s];
@@ -4013,8 +3920,7 @@ void plan_presence(const pgpu_query_desc* q, Packer& pk, DevParams& p, LaunchPla
   }
   // the keep bits' chunk: a wave's 64 lanes hold one row word each; PGPU_PRESENCE_CHUNK_WORDS (read per plan) makes
   // it shorter, so that tests reach a range's second chunk at their sizes
-  const char* cwe = getenv("PGPU_PRESENCE_CHUNK_WORDS");
-  const int cw = cwe && *cwe ? atoi(cwe) : 64;
+  const int cw = pk.env.presence_chunk_words;
   p.rd_skip = std::min(64, std::max(1, cw));
 }
 
@@ -4025,8 +3931,11 @@ void plan_presence(const pgpu_query_desc* q, Packer& pk, DevParams& p, LaunchPla
 int pack_and_plan(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_layout& L, Packer& pk, DevParams& p,
                   LaunchPlan& pl) {
   LeadInfo li;
+  PlanEnv env;
+  env.read();  // once per submit; a test that changes a switch between two submits still sees the change
   for (int attempt = 0; attempt < 2; ++attempt) {
-    pk = Packer();
+    pk.clear();
+    pk.env = env;
     pl = LaunchPlan();
     li.allow = attempt == 0;
     const double tp0 = HostTiming::us();
@@ -4035,13 +3944,17 @@ int pack_and_plan(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_
     if (rc == kLeadRetry && attempt == 0) continue;  // a lead leaf that did not pack as one: query order
     if (rc) return rc;
     // host only: which kernel, grid and LDS size, and with them whether the query is one launch or three
+    const double tl0 = HostTiming::us();
     drop_reference_replay(q, pk);
     rc = plan_launch(ctx->num_cus, q, L, pk, p, pl);
+    host_timing().add(HostTiming::kPlanLaunch, tl0, HostTiming::us());
     if (rc) return rc;
     if (!li.switched || p.direct == PGPU_KV_RDIRECT) break;
   }
   SkipInfo si;
+  const double ts0 = HostTiming::us();
   plan_presence(q, pk, p, pl, &si);
+  host_timing().add(HostTiming::kPresence, ts0, HostTiming::us());
   if (plan_trace_on()) trace_plan(pk, p, pl, li, si);
   return PGPU_OK;
 }
@@ -4620,7 +4533,7 @@ pgpu_query* make_query_handle(pgpu_context* ctx, const pgpu_query_desc* q, const
                         nd.op == PGPU_F_RAW_SCAN || nd.op == PGPU_F_RANGE_INDEX;
       if (!leaf) continue;
       const HostColumn* mv = mv_scan_column(q, sp, nd);
-      leaf_off.push_back(mv ? mv->mv_offsets.data() : nullptr);
+      if (qq->exact_filter) leaf_off.push_back(mv ? mv->mv_offsets.data() : nullptr);  // (kept only by the replay)
       nmv += mv != nullptr;
     }
     if (nmv && sp.num_filter_nodes == 1) qq->mv_entries += sp.segment->cols[sp.column_map[sp.filter[0].column]].mv_values;
@@ -4657,13 +4570,13 @@ int pgpu_lead_model(int32_t bits_a, double rho_dense, int32_t residual_kind, int
   if (bits_a < 0 || bits_b < 1 || bits_b > 31 || num_dense_scans < 0 || residual_kind < PGPU_LEAD_RESID_NONE ||
       residual_kind > PGPU_LEAD_RESID_OTHER)
     return fail(PGPU_E_INVALID, "lead model: bits %d / %d, residual kind %d", bits_a, bits_b, residual_kind);
-  std::vector<std::pair<uint64_t, uint64_t>> r;
+  segplan::SmallVec<segplan::Run, segplan::kMaskRuns> r;
   for (int k = 0; k < num_runs; ++k) {
     if (runs[2 * k + 1] <= runs[2 * k]) continue;
     if (runs[2 * k + 1] > (1ull << bits_b)) return fail(PGPU_E_INVALID, "lead model: id run past 2^%d", bits_b);
-    r.emplace_back(runs[2 * k], runs[2 * k + 1]);
+    r.push_back(segplan::Run{runs[2 * k], runs[2 * k + 1]});
   }
-  lead_model(bits_a, rho_dense, residual_kind, num_dense_scans, bits_b, sel_b, r, out);
+  segplan::lead_model(bits_a, rho_dense, residual_kind, num_dense_scans, bits_b, sel_b, r.data(), r.size(), out);
   return PGPU_OK;
 }
 
@@ -4750,7 +4663,8 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
   if (!tws && (!dev_table || table_bytes < need))
     return fail(PGPU_E_INVALID, "table buffer %llu bytes < %llu needed", (unsigned long long)table_bytes,
                 (unsigned long long)need);
-  Packer pk;
+  static thread_local Packer tl_packer;  // this thread's submit scratch (see Packer, PlanScratch)
+  Packer& pk = tl_packer;
   DevParams p;
   LaunchPlan pl;
   rc = pack_and_plan(ctx, q, L, pk, p, pl);
@@ -4805,7 +4719,10 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
     return rc;
   }
   const hipEvent_t done = kernel_is_done ? pick.ev1 : ws->done;  // (= pick.done)
+  const double th0 = HostTiming::us();
   pgpu_query* qq = make_query_handle(ctx, q, pk, p, pl.grid, ws, st, done, eager);
+  host_timing().mark = HostTiming::us();
+  host_timing().add(HostTiming::kHandle, th0, host_timing().mark);
   qq->presence_builds = std::move(pl.presence_builds);
   qq->ev0 = pick.ev0;
   qq->ev1 = pick.ev1;
@@ -5545,29 +5462,18 @@ int pgpu_query_collect_mode(pgpu_query* qq, uint64_t inner_keys, const double* p
 //     core/operator/filter/FilterOperatorUtils.java:42-221).
 namespace {
 
-struct Leaf {
-  int kind;  // 0 EMPTY, 1 ALL, 2 SCAN, 3 INV, 4 SORTED
-  bool exclusive = false;
-  bool range = false;  // RANGE evaluator [start, end)
-  int32_t start = 0, end = 0;
-  std::vector<int32_t> ids;  // SET evaluator: matching ids, or non-matching ids for exclusive predicates
-};
-
+// One node of a segment's planned filter.  Flat: a leaf's ids and a node's children are ranges of ExprScratch's
+// pools, so planning a segment allocates nothing once the pools have grown to a query's size.
 struct PlanNode {
   int kind;  // 0 EMPTY, 1 ALL, 2 SCAN, 3 INV, 4 SORTED, 5 AND, 6 OR, 7 NOT
   int column = -1;
-  Leaf leaf;
-  std::vector<PlanNode> kids;
-  int priority() const {
-    switch (kind) {
-      case 4: return 0;
-      case 3: return 1;
-      case 5: return 3;
-      case 6: return 4;
-      case 7: return kids[0].priority();
-      default: return 5;
-    }
-  }
+  // leaf
+  bool exclusive = false;
+  bool range = false;  // RANGE evaluator [start, end)
+  int32_t start = 0, end = 0;
+  int ids_off = 0, ids_n = 0;  // SET evaluator: matching ids, or non-matching ids for exclusive predicates
+  // AND / OR / NOT: children, adjacent in ExprScratch::arena
+  int kid_off = 0, kid_n = 0;
 };
 
 // BaseImmutableDictionary.insertionIndexOf: >= 0 exact match index, else -(insertion point + 1)
@@ -5598,30 +5504,52 @@ int64_t insertion_index(const HostColumn& c, const pgpu_literal& lit) {
   return lo < n && at(lo) == key ? lo : -(lo + 1);
 }
 
-// PredicateEvaluatorProvider.getPredicateEvaluator for dictionary-encoded columns
-Leaf evaluate(const HostColumn& c, const pgpu_expr_node& x) {
-  Leaf l;
+// Descriptor copy whose segment plans carry the filter programs planned from `expr`: one node array and one id pool
+// for all segments (pointers patched behind the last append), beside the planner's own pools.  One per submitting
+// thread, reused from submit to submit like PlanScratch; the submit copies what it keeps.
+struct PlannedDesc {
+  pgpu_query_desc q;
+  std::vector<pgpu_segment_plan> plans;
+  std::vector<pgpu_filter_node> nodes;
+  std::vector<int32_t> pool;
+  std::vector<std::pair<int, int>> seg_nodes;  // per segment: [begin, begin + count) of `nodes`
+  std::vector<std::pair<int, int>> id_at;      // (node, offset in `pool`) of every node with ids
+  // planner pools of the segment being planned
+  std::vector<PlanNode> arena;
+  std::vector<int32_t> ids;
+};
+
+// PredicateEvaluatorProvider.getPredicateEvaluator for dictionary-encoded columns (set ids appended to `ids`)
+PlanNode evaluate(const HostColumn& c, const pgpu_expr_node& x, std::vector<int32_t>& ids) {
+  PlanNode l;
+  l.kind = 0;
   const int32_t card = c.dict_card;
   auto index_of = [&](const pgpu_literal& v) -> int32_t {
     const int64_t i = insertion_index(c, v);
     return i >= 0 ? (int32_t)i : -1;
   };
+  auto one_id = [&](int32_t i) {
+    l.ids_off = (int)ids.size();
+    l.ids_n = 1;
+    ids.push_back(i);
+  };
   auto id_set = [&]() {
-    std::vector<int32_t> ids;
+    const size_t mark = ids.size();
     for (int k = 0; k < x.num_values; ++k) {
       const int32_t i = index_of(x.values[k]);
       if (i >= 0) ids.push_back(i);
     }
-    std::sort(ids.begin(), ids.end());
-    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-    return ids;
+    std::sort(ids.begin() + mark, ids.end());
+    ids.erase(std::unique(ids.begin() + mark, ids.end()), ids.end());
+    l.ids_off = (int)mark;
+    l.ids_n = (int)(ids.size() - mark);
   };
   switch (x.pred) {
     case PGPU_P_EQ: {
       const int32_t i = x.num_values > 0 ? index_of(x.values[0]) : -1;
       if (i < 0) { l.kind = 0; return l; }
       l.kind = card == 1 ? 1 : 2;
-      l.ids = {i};
+      one_id(i);
       return l;
     }
     case PGPU_P_NOT_EQ: {
@@ -5629,17 +5557,17 @@ Leaf evaluate(const HostColumn& c, const pgpu_expr_node& x) {
       if (i < 0) { l.kind = 1; return l; }
       l.kind = card == 1 ? 0 : 2;
       l.exclusive = true;
-      l.ids = {i};
+      one_id(i);
       return l;
     }
     case PGPU_P_IN:
-      l.ids = id_set();
-      l.kind = l.ids.empty() ? 0 : ((int32_t)l.ids.size() == card ? 1 : 2);
+      id_set();
+      l.kind = l.ids_n == 0 ? 0 : (l.ids_n == card ? 1 : 2);
       return l;
     case PGPU_P_NOT_IN:
-      l.ids = id_set();
+      id_set();
       l.exclusive = true;
-      l.kind = l.ids.empty() ? 1 : ((int32_t)l.ids.size() == card ? 0 : 2);
+      l.kind = l.ids_n == 0 ? 1 : (l.ids_n == card ? 0 : 2);
       return l;
     default: {  // RANGE
       int64_t start = 0, end = card;
@@ -5667,6 +5595,7 @@ struct ExprPlanner {
   const pgpu_segment* seg;
   const pgpu_expr_node* x;
   int n;
+  PlannedDesc& out;
   int err = PGPU_OK;
 
   const HostColumn* column(int qc) {
@@ -5681,116 +5610,144 @@ struct ExprPlanner {
     return &c;
   }
 
+  int priority(const PlanNode& o) const {
+    const PlanNode* p = &o;
+    while (p->kind == 7) p = &out.arena[p->kid_off];
+    switch (p->kind) {
+      case 4: return 0;
+      case 3: return 1;
+      case 5: return 3;
+      case 6: return 4;
+      default: return 5;
+    }
+  }
+
   // FilterPlanNode.constructPhysicalOperator over the subtree starting at node i; *next = first node after it
   PlanNode build(int i, int* next) {
-    PlanNode out;
-    out.kind = 0;
-    if (i >= n) { err = fail(PGPU_E_INVALID, "malformed filter expression"); *next = n; return out; }
+    PlanNode o;
+    o.kind = 0;
+    if (i >= n) { err = fail(PGPU_E_INVALID, "malformed filter expression"); *next = n; return o; }
     const pgpu_expr_node& e = x[i];
     if (e.op == PGPU_X_AND || e.op == PGPU_X_OR) {
       const bool is_and = e.op == PGPU_X_AND;
       int j = i + 1;
-      std::vector<PlanNode> kids;
+      segplan::SmallVec<PlanNode, segplan::kKidsCap> kids;  // (inline; more children spill to the heap)
       bool empty = false, all = false;
       for (int k = 0; k < e.num_children && !err; ++k) {
-        PlanNode ch = build(j, &j);
+        const PlanNode ch = build(j, &j);
         if (is_and) {
           if (ch.kind == 0) empty = true;
-          else if (ch.kind != 1) kids.push_back(std::move(ch));
+          else if (ch.kind != 1) kids.push_back(ch);
         } else {
           if (ch.kind == 1) all = true;
-          else if (ch.kind != 0) kids.push_back(std::move(ch));
+          else if (ch.kind != 0) kids.push_back(ch);
         }
       }
       *next = j;
-      if (is_and ? empty : all) { out.kind = is_and ? 0 : 1; return out; }
-      if (kids.empty()) { out.kind = is_and ? 1 : 0; return out; }
-      if (kids.size() == 1) return std::move(kids[0]);
-      if (is_and)
-        std::stable_sort(kids.begin(), kids.end(),
-                         [](const PlanNode& a, const PlanNode& b) { return a.priority() < b.priority(); });
-      out.kind = is_and ? 5 : 6;
-      out.kids = std::move(kids);
-      return out;
+      if (is_and ? empty : all) { o.kind = is_and ? 0 : 1; return o; }
+      if (kids.empty()) { o.kind = is_and ? 1 : 0; return o; }
+      if (kids.size() == 1) return kids[0];
+      if (is_and) {  // by priority, equal ones in query order: a stable insertion sort
+        for (int a = 1; a < kids.size(); ++a) {
+          const PlanNode k = kids[a];
+          const int pk = priority(k);
+          int b = a;
+          for (; b > 0 && priority(kids[b - 1]) > pk; --b) kids[b] = kids[b - 1];
+          kids[b] = k;
+        }
+      }
+      o.kind = is_and ? 5 : 6;
+      o.kid_off = (int)out.arena.size();
+      o.kid_n = kids.size();
+      out.arena.insert(out.arena.end(), kids.begin(), kids.end());
+      return o;
     }
     if (e.op == PGPU_X_NOT) {
-      PlanNode ch = build(i + 1, next);
-      if (ch.kind == 1) { out.kind = 0; return out; }
-      if (ch.kind == 0) { out.kind = 1; return out; }
-      out.kind = 7;
-      out.kids.push_back(std::move(ch));
-      return out;
+      const PlanNode ch = build(i + 1, next);
+      if (ch.kind == 1) { o.kind = 0; return o; }
+      if (ch.kind == 0) { o.kind = 1; return o; }
+      o.kind = 7;
+      o.kid_off = (int)out.arena.size();
+      o.kid_n = 1;
+      out.arena.push_back(ch);
+      return o;
     }
     *next = i + 1;
     const HostColumn* c = column(e.column);
-    if (!c) return out;
-    Leaf l = evaluate(*c, e);
-    out.column = e.column;
-    if (l.kind == 0 || l.kind == 1) { out.kind = l.kind; return out; }
-    if (c->kind == PGPU_COL_SORTED) out.kind = 4;
-    else if (e.pred != PGPU_P_RANGE && c->inv_card > 0) out.kind = 3;
-    else out.kind = 2;
-    out.leaf = std::move(l);
-    return out;
+    if (!c) return o;
+    PlanNode l = evaluate(*c, e, out.ids);
+    l.column = e.column;
+    if (l.kind == 0 || l.kind == 1) {
+      o.kind = l.kind;
+      o.column = e.column;
+      return o;
+    }
+    if (c->kind == PGPU_COL_SORTED) l.kind = 4;
+    else if (e.pred != PGPU_P_RANGE && c->inv_card > 0) l.kind = 3;
+    else l.kind = 2;
+    return l;
   }
 
-  // emit the prefix-order pgpu_filter_node program; id lists go to `pool` (offsets patched afterwards)
-  void emit(const PlanNode& o, std::vector<pgpu_filter_node>& nodes, std::vector<int32_t>& pool,
-            std::vector<std::pair<int, int>>& id_at) {
+  // emit the prefix-order pgpu_filter_node program into out.nodes; id lists go to out.pool (pointers patched
+  // by plan_expr behind the last segment)
+  void emit(const PlanNode& o) {
+    std::vector<pgpu_filter_node>& nodes = out.nodes;
+    std::vector<int32_t>& pool = out.pool;
     pgpu_filter_node nd;
     memset(&nd, 0, sizeof(nd));
-    auto with_ids = [&](const std::vector<int32_t>& v, int count) {
-      id_at.emplace_back((int)nodes.size(), (int)pool.size());
-      pool.insert(pool.end(), v.begin(), v.end());
+    auto with_ids = [&](const int32_t* v, int nv, int count) {
+      out.id_at.emplace_back((int)nodes.size(), (int)pool.size());
+      pool.insert(pool.end(), v, v + nv);
       nd.num_ids = count;
     };
+    const int32_t* ids = out.ids.data() + o.ids_off;
     switch (o.kind) {
       case 0: case 1:
         nd.op = o.kind == 0 ? PGPU_F_EMPTY : PGPU_F_MATCH_ALL;
         nodes.push_back(nd);
         return;
       case 2: {
-        const Leaf& l = o.leaf;
         nd.op = PGPU_F_SCAN;
         nd.column = o.column;
-        nd.negate = l.exclusive ? 1 : 0;
-        if (l.range) {
-          nd.pred = PGPU_PRED_RANGE; nd.lo = l.start; nd.hi = l.end;
-        } else if (!l.ids.empty() && l.ids.back() - l.ids.front() + 1 == (int32_t)l.ids.size()) {
-          nd.pred = PGPU_PRED_RANGE; nd.lo = l.ids.front(); nd.hi = l.ids.back() + 1;
+        nd.negate = o.exclusive ? 1 : 0;
+        if (o.range) {
+          nd.pred = PGPU_PRED_RANGE; nd.lo = o.start; nd.hi = o.end;
+        } else if (o.ids_n > 0 && ids[o.ids_n - 1] - ids[0] + 1 == o.ids_n) {
+          nd.pred = PGPU_PRED_RANGE; nd.lo = ids[0]; nd.hi = ids[o.ids_n - 1] + 1;
         } else {
           nd.pred = PGPU_PRED_SET;
-          with_ids(l.ids, (int)l.ids.size());
+          with_ids(ids, o.ids_n, o.ids_n);
         }
         nodes.push_back(nd);
         return;
       }
       case 3: {  // INV: matching ids, or the non-matching ids of an exclusive predicate (flipped)
-        const Leaf& l = o.leaf;
         nd.op = PGPU_F_INVERTED;
         nd.column = o.column;
-        nd.negate = l.exclusive ? 1 : 0;
-        with_ids(l.ids, (int)l.ids.size());
+        nd.negate = o.exclusive ? 1 : 0;
+        with_ids(ids, o.ids_n, o.ids_n);
         nodes.push_back(nd);
         return;
       }
       case 4: {  // SORTED: doc ranges of the (non-)matching ids, adjacent ranges merged
-        const Leaf& l = o.leaf;
         const HostColumn& c = seg->cols[sp->column_map[o.column]];
-        std::vector<int32_t> flat;
-        if (l.range) {
-          flat = {c.sorted_pairs[2 * l.start], c.sorted_pairs[2 * (l.end - 1) + 1]};
+        out.id_at.emplace_back((int)nodes.size(), (int)pool.size());
+        const size_t mark = pool.size();
+        if (o.range) {
+          pool.push_back(c.sorted_pairs[2 * o.start]);
+          pool.push_back(c.sorted_pairs[2 * (o.end - 1) + 1]);
         } else {
-          for (int32_t id : l.ids) {
+          for (int k = 0; k < o.ids_n; ++k) {
+            const int32_t id = ids[k];
             const int32_t s0 = c.sorted_pairs[2 * id], e0 = c.sorted_pairs[2 * id + 1];
-            if (!flat.empty() && s0 == flat.back() + 1) flat.back() = e0;
-            else { flat.push_back(s0); flat.push_back(e0); }
+            if (pool.size() > mark && s0 == pool.back() + 1) pool.back() = e0;
+            else { pool.push_back(s0); pool.push_back(e0); }
           }
         }
         nd.op = PGPU_F_SORTED;
         nd.column = o.column;
-        nd.negate = (l.exclusive && !l.range) ? 1 : 0;
-        with_ids(flat, (int)flat.size() / 2);
+        nd.negate = (o.exclusive && !o.range) ? 1 : 0;
+        nd.num_ids = (int)(pool.size() - mark) / 2;
         nodes.push_back(nd);
         return;
       }
@@ -5798,8 +5755,8 @@ struct ExprPlanner {
         const bool a = o.kind == 5;
         nd.op = a ? PGPU_F_AND_BEGIN : PGPU_F_OR_BEGIN;
         nodes.push_back(nd);
-        for (const PlanNode& ch : o.kids) {
-          emit(ch, nodes, pool, id_at);
+        for (int k = 0; k < o.kid_n; ++k) {
+          emit(PlanNode(out.arena[o.kid_off + k]));
           pgpu_filter_node ce;
           memset(&ce, 0, sizeof(ce));
           ce.op = a ? PGPU_F_AND_CHILD_END : PGPU_F_OR_CHILD_END;
@@ -5814,43 +5771,46 @@ struct ExprPlanner {
       default:
         nd.op = PGPU_F_NOT;
         nodes.push_back(nd);
-        emit(o.kids[0], nodes, pool, id_at);
+        emit(PlanNode(out.arena[o.kid_off]));
         return;
     }
   }
-};
-
-// Descriptor copy whose segment plans carry the filter programs planned from `expr`.
-struct PlannedDesc {
-  pgpu_query_desc q;
-  std::vector<pgpu_segment_plan> plans;
-  std::vector<std::vector<pgpu_filter_node>> nodes;
-  std::vector<std::vector<int32_t>> pools;
 };
 
 int plan_expr(const pgpu_query_desc* q, const pgpu_expr_node* expr, int32_t num_nodes, PlannedDesc& out) {
   if (!q || (!expr && num_nodes > 0) || num_nodes < 0) return fail(PGPU_E_INVALID, "null argument");
   out.q = *q;
   out.plans.assign(q->segments, q->segments + q->num_segments);
-  out.nodes.resize(q->num_segments);
-  out.pools.resize(q->num_segments);
+  out.nodes.clear();
+  out.pool.clear();
+  out.id_at.clear();
+  out.seg_nodes.assign((size_t)std::max(0, q->num_segments), std::make_pair(0, 0));
+  // (a reservation from the expression's size, not a bound: an AND of k leaves emits 2k + 2 nodes)
+  out.nodes.reserve((size_t)std::max(0, q->num_segments) * (3 * (size_t)num_nodes + 1));
   for (int s = 0; s < q->num_segments; ++s) {
     pgpu_segment_plan& sp = out.plans[s];
     sp.filter = nullptr;
     sp.num_filter_nodes = 0;
     if (num_nodes == 0) continue;
     if (!sp.segment || !sp.column_map) return fail(PGPU_E_INVALID, "segment %d plan", s);
-    ExprPlanner pl{q, &sp, sp.segment, expr, num_nodes};
+    out.arena.clear();
+    out.ids.clear();
+    ExprPlanner pl{q, &sp, sp.segment, expr, num_nodes, out};
     int next = 0;
-    PlanNode root = pl.build(0, &next);
+    const PlanNode root = pl.build(0, &next);
     if (pl.err) return pl.err;
     if (next != num_nodes) return fail(PGPU_E_INVALID, "filter expression has %d trailing nodes", num_nodes - next);
     if (root.kind == 1) continue;  // match all: no program
-    std::vector<std::pair<int, int>> id_at;
-    pl.emit(root, out.nodes[s], out.pools[s], id_at);
-    for (const auto& ia : id_at) out.nodes[s][ia.first].ids = out.pools[s].data() + ia.second;
-    sp.filter = out.nodes[s].data();
-    sp.num_filter_nodes = (int32_t)out.nodes[s].size();
+    const int begin = (int)out.nodes.size();
+    pl.emit(root);
+    out.seg_nodes[s] = std::make_pair(begin, (int)out.nodes.size() - begin);
+  }
+  // behind the last append: neither array moves any more
+  for (const auto& ia : out.id_at) out.nodes[ia.first].ids = out.pool.data() + ia.second;
+  for (int s = 0; s < q->num_segments; ++s) {
+    if (out.seg_nodes[s].second == 0) continue;
+    out.plans[s].filter = out.nodes.data() + out.seg_nodes[s].first;
+    out.plans[s].num_filter_nodes = (int32_t)out.seg_nodes[s].second;
   }
   out.q.segments = out.plans.data();
   return PGPU_OK;
@@ -5919,12 +5879,15 @@ int pgpu_query_submit_ordered(pgpu_context* ctx, const pgpu_query_desc* q, const
   if (!ctx || !q || !out_query) return fail(PGPU_E_INVALID, "null argument");
   if (!expr) return submit_impl(ctx, q, order, out_query);
   const double t0 = HostTiming::us();
-  PlannedDesc pd;
+  static thread_local PlannedDesc pd;  // this thread's submit scratch (see PlannedDesc)
   int rc = plan_expr(q, expr, num_nodes, pd);
   if (rc) return rc;
   host_timing().add(0, t0, HostTiming::us());
+  host_timing().mark = 0;
   rc = submit_impl(ctx, &pd.q, order, out_query);  // the descriptor is copied by the submit
-  host_timing().add(5, t0, HostTiming::us());
+  const double t1 = HostTiming::us();
+  if (host_timing().mark > 0) host_timing().add(HostTiming::kTeardown, host_timing().mark, t1);
+  host_timing().add(5, t0, t1);
   host_timing().done();
   return rc;
 }
