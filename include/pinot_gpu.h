@@ -724,6 +724,41 @@ int pgpu_query_launch_expr(pgpu_context* ctx, const pgpu_query_desc* q, const pg
 int pgpu_query_submit_ordered(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_expr_node* expr,
                               int32_t num_nodes, const pgpu_topk* order, pgpu_query** out_query);
 
+/* ---- prepared queries: plan once, submit many times --------------------------------------------------------------
+ * The same query submitted again over the same segments (a dashboard's repeated query) need not be planned again.
+ * pgpu_query_prepare takes what pgpu_query_submit_ordered takes, deep-copies everything the descriptor, the
+ * expression and the order point to (no caller memory is read afterwards) and plans once: every error the submit
+ * would return comes back here, with the same pgpu_last_error text, and *out is then left untouched.
+ * pgpu_prepared_submit is pgpu_query_submit_ordered with the deadline given per submit (0 = none; the descriptor's
+ * own deadline_ms is ignored) and the matched-segments buffer registered in the same call (NULL = none; else
+ * num_segments must be the descriptor's).  The pgpu_query it returns is an ordinary one -- wait, collect*, cancel,
+ * matched_segments, release -- and does not point into the prepared object: releasing the prepared handle while its
+ * queries are in flight is legal.  Concurrent submits of one handle are legal.
+ * A submit reuses the handle's cached plan only when that plan provably equals what a fresh run would produce: the
+ * per-plan switches read now equal the ones it was planned under, nothing else the planners read has changed
+ * (segments or remap buffers released, derived copies, presence rows becoming ready or declined), the plan did nothing
+ * but plan (it neither counted an ask for presence rows nor waits for their build), and PGPU_PLAN_TRACE is off.
+ * Otherwise the submit plans afresh from the owned copy, exactly as pgpu_query_submit_ordered would, and keeps the
+ * new plan if it may.  Naming a segment or remap buffer released meanwhile is the caller's error, as with
+ * pgpu_query_submit.  Queries whose literals differ are different queries: nothing is shared between them.
+ * pgpu_prepared_counts: plans made (the prepare's included), submits served by a plan an earlier submit had used
+ * (hits), and submits whose plan could not be kept (uncached).  pgpu_prepared_live: handles not yet released, in
+ * this process (diagnostic). */
+typedef struct pgpu_prepared pgpu_prepared;
+struct pgpu_prepared_counts {
+  int64_t plans;
+  int64_t hits;
+  int64_t uncached;
+};
+int pgpu_query_prepare(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_expr_node* expr, int32_t num_nodes,
+                       const pgpu_topk* order, pgpu_prepared** out);
+int pgpu_prepared_submit(pgpu_prepared* prepared, int64_t deadline_ms, uint8_t* matched_out, int32_t num_segments,
+                         pgpu_query** out_query);
+/* (the struct shares the function's name, so it is always written with its tag) */
+int pgpu_prepared_counts(const pgpu_prepared* prepared, struct pgpu_prepared_counts* out);
+int pgpu_prepared_release(pgpu_prepared* prepared);
+int64_t pgpu_prepared_live(void);
+
 /* ---- node-level combine: one process, several GPUs, RCCL inside the library ------------------------------------
  * For a server that drives all GPUs of a node from one process (a JVM): contexts for the given HIP ordinals and
  * one RCCL communicator clique over them (RCCL is loaded on first use).  Segments are uploaded through each

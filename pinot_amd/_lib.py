@@ -157,6 +157,12 @@ class ExprNode(C.Structure):
                 ("values", C.POINTER(Literal))]
 
 
+class PreparedCounts(C.Structure):
+    """struct pgpu_prepared_counts: plans made, submits served by an already used plan, submits whose plan was not
+    kept (pgpu_prepared_counts)."""
+    _fields_ = [("plans", C.c_int64), ("hits", C.c_int64), ("uncached", C.c_int64)]
+
+
 PGPU_LEAD_RESID_NONE, PGPU_LEAD_RESID_B, PGPU_LEAD_RESID_OTHER = range(3)
 
 
@@ -265,6 +271,12 @@ SIGNATURES = [
     ("pgpu_query_submit_expr", C.c_int, [_P, C.POINTER(QueryDesc), C.POINTER(ExprNode), C.c_int32, C.POINTER(_P)]),
     ("pgpu_query_submit_ordered", C.c_int, [_P, C.POINTER(QueryDesc), C.POINTER(ExprNode), C.c_int32,
                                             C.POINTER(TopK), C.POINTER(_P)]),
+    ("pgpu_query_prepare", C.c_int, [_P, C.POINTER(QueryDesc), C.POINTER(ExprNode), C.c_int32, C.POINTER(TopK),
+                                     C.POINTER(_P)]),
+    ("pgpu_prepared_submit", C.c_int, [_P, C.c_int64, C.POINTER(C.c_uint8), C.c_int32, C.POINTER(_P)]),
+    ("pgpu_prepared_counts", C.c_int, [_P, C.POINTER(PreparedCounts)]),
+    ("pgpu_prepared_release", C.c_int, [_P]),
+    ("pgpu_prepared_live", C.c_int64, []),
     ("pgpu_query_launch_expr", C.c_int, [_P, C.POINTER(QueryDesc), C.POINTER(ExprNode), C.c_int32, _P, _P,
                                          C.c_uint64, C.POINTER(_P)]),
     ("pgpu_query_execute", C.c_int, [_P, C.POINTER(QueryDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -340,6 +352,42 @@ def check(rc: int) -> None:
         if rc == PGPU_E_CANCELLED:
             raise QueryCancelledError(rc, msg)
         raise PinotGpuError(rc, msg)
+
+
+class PreparedQuery:
+    """Owns a pgpu_prepared handle: made at the first submit (so that a query the library refuses is refused where
+    pgpu_query_submit_ordered would refuse it), released when the last reference goes or by release()."""
+    __slots__ = ("handle",)
+
+    def __init__(self):
+        self.handle = None
+
+    def submit(self, ctx_handle, desc, expr, order, matched, num_segments: int):
+        """pgpu_prepared_submit with the descriptor's deadline; the first call prepares.  Returns the query handle."""
+        lib = load()
+        if self.handle is None:
+            h = C.c_void_p()
+            check(lib.pgpu_query_prepare(ctx_handle, C.byref(desc), expr[0] if expr is not None else None,
+                                         expr[1] if expr is not None else 0,
+                                         C.byref(order) if order is not None else None, C.byref(h)))
+            self.handle = h
+        q = C.c_void_p()
+        check(lib.pgpu_prepared_submit(self.handle, desc.deadline_ms, matched.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                       num_segments, C.byref(q)))
+        return q
+
+    def counts(self) -> PreparedCounts:
+        out = PreparedCounts()
+        if self.handle is not None:
+            check(load().pgpu_prepared_counts(self.handle, C.byref(out)))
+        return out
+
+    def release(self) -> None:
+        h, self.handle = self.handle, None
+        if h is not None and _lib is not None:
+            _lib.pgpu_prepared_release(h)
+
+    __del__ = release
 
 
 def folded_layout_of(layout: TableLayout, inner_keys: int, num_percentiles: int, reducers: int) -> TableLayout:

@@ -279,6 +279,7 @@ struct PinnedMem {
 struct HostTiming {
   enum { kLead = 6, kSegPlan, kPlanLaunch, kPresence, kHandle, kTeardown, kBuckets };
   int every = 0, n = 0;
+  int prepared = 0, cached = 0;  // of the window's submits: through pgpu_prepared_submit, and from a cached plan
   double acc[kBuckets] = {};
   double mark = 0;  // launch_impl: the handle is made, only destructors follow
   HostTiming() {
@@ -299,7 +300,9 @@ struct HostTiming {
     fprintf(stderr, "[pgpu host] of which (us): lead %.1f segplan %.1f plan_launch %.1f presence %.1f handle %.1f "
             "teardown %.1f\n", acc[kLead] / n, acc[kSegPlan] / n, acc[kPlanLaunch] / n, acc[kPresence] / n,
             acc[kHandle] / n, acc[kTeardown] / n);
-    n = 0;
+    fprintf(stderr, "[pgpu host] prepared submits from a cached plan: %d of %d submits (%d prepared)\n", cached, n,
+            prepared);
+    n = prepared = cached = 0;
     for (double& a : acc) a = 0;
   }
 };
@@ -412,6 +415,10 @@ struct pgpu_context {
   // (atomic: a budget set from one thread may meet another thread's seal; a new budget governs later seals only --
   // copies already built are kept until their segment is released)
   std::atomic<uint64_t> derived_budget{UINT64_MAX};
+  // Bumped by everything that changes what the planners read beyond a query's descriptor and the per-plan switches:
+  // derived copies built, evicted or re-budgeted, segments and remap buffers released, presence rows becoming ready
+  // or declined.  A prepared query's cached plan carries the epoch it was planned at (pgpu_prepared_submit).
+  std::atomic<uint64_t> plan_epoch{0};
   ~pgpu_context() {
     pool.clear();
     if (qstream) (void)hipStreamDestroy(qstream);
@@ -1264,6 +1271,7 @@ void presence_start(PresenceState& ps, hipStream_t st, int max_wgs) {
   }
   if (ok) ps.wpr = (int32_t)wpr;
   ps.state.store(ok ? PresenceState::kBuilding : PresenceState::kDeclined, std::memory_order_release);
+  ps.ctx->plan_epoch.fetch_add(1);  // (a derived copy built or declined: cached plans are planned again)
 }
 
 // The column's finished presence rows, or nullptr.  Never waits: a build in flight is asked once whether it is done.
@@ -1278,6 +1286,7 @@ const uint32_t* presence_ready(const HostColumn& c, int32_t* wpr) {
       if (hipEventQuery(ps->built) == hipSuccess) {
         ps->state.store(PresenceState::kReady, std::memory_order_release);
         st = PresenceState::kReady;
+        ps->ctx->plan_epoch.fetch_add(1);
       } else {
         (void)hipGetLastError();  // ("not ready" is no error of the launches that follow)
       }
@@ -1387,6 +1396,7 @@ int pgpu_segment_seal(pgpu_segment* seg) {
   }
   HIP_TRY(hipDeviceSynchronize());
   seg->sealed = true;
+  seg->ctx->plan_epoch.fetch_add(1);  // (derived copies built)
   return PGPU_OK;
 }
 
@@ -1447,6 +1457,7 @@ int pgpu_segment_add_group_dictionary(pgpu_segment* seg, int32_t raw_column, int
   dictionary_hash(le, c.dict_hash);
   c.hdict = std::move(le);
   if (seg->sealed) {
+    seg->ctx->plan_epoch.fetch_add(1);  // (a sealed segment's slot filled)
     const int rc = seal_column(seg, (size_t)dict_column);
     if (rc) return rc;
   }
@@ -1473,6 +1484,7 @@ int pgpu_segment_add_docid_column(pgpu_segment* seg, int32_t column) {
   c.dict_bytes = 4ull * (uint64_t)n;
   c.max_abs = n > 0 ? (double)(n - 1) : 0.0;
   if (seg->sealed) {
+    seg->ctx->plan_epoch.fetch_add(1);  // (a sealed segment's slot filled)
     const int rc = seal_column(seg, (size_t)column);
     if (rc) return rc;
   }
@@ -1526,6 +1538,8 @@ int pgpu_segment_device_bytes_ex(const pgpu_segment* seg, pgpu_segment_bytes* ou
 }
 
 int pgpu_segment_set_derived(pgpu_segment* seg, int32_t column, int32_t flags) {
+  // (whatever the call's outcome -- a sealed segment refuses it: cached plans naming the segment are planned again)
+  if (seg) seg->ctx->plan_epoch.fetch_add(1);
   const int rc = check_column(seg, column);
   if (rc) return rc;
   if (flags < 0 || flags > PGPU_DERIVE_ALL) return fail(PGPU_E_INVALID, "derived-copy flags %d", flags);
@@ -1537,6 +1551,7 @@ int pgpu_segment_set_derived(pgpu_segment* seg, int32_t column, int32_t flags) {
 int pgpu_context_set_derived_budget(pgpu_context* ctx, uint64_t bytes) {
   if (!ctx) return fail(PGPU_E_INVALID, "null context");
   ctx->derived_budget = bytes;
+  ctx->plan_epoch.fetch_add(1);
   return PGPU_OK;
 }
 
@@ -1564,6 +1579,7 @@ int pgpu_segment_release(pgpu_segment* seg) {
     }
   }
   seg->ctx->derived_bytes -= derived;
+  seg->ctx->plan_epoch.fetch_add(1);
   delete seg;
   return PGPU_OK;
 }
@@ -1584,6 +1600,7 @@ int pgpu_remap_upload(pgpu_context* ctx, const int32_t* map, int32_t length, pgp
 }
 
 int pgpu_buffer_release(pgpu_buffer* buf) {
+  if (buf && buf->ctx) buf->ctx->plan_epoch.fetch_add(1);
   delete buf;
   return PGPU_OK;
 }
@@ -1806,7 +1823,16 @@ struct PlanEnv {
   double cand_density = 0;     // PGPU_CAND_DENSITY (kCandDensity when unset)
   int presence_chunk_words = 64;  // PGPU_PRESENCE_CHUNK_WORDS
   int64_t lead_switch_bytes = 0, presence_switch_bytes = 0;
+  int presence_after = 2;      // PGPU_PRESENCE_AFTER
   void read();
+  // (field by field: a prepared query compares the switches it was planned under with the ones read now)
+  bool operator==(const PlanEnv& o) const {
+    return progbits == o.progbits && always_replay == o.always_replay && no_rstream == o.no_rstream &&
+           no_rkey == o.no_rkey && rkey_ids == o.rkey_ids && no_rprog == o.no_rprog && no_cand == o.no_cand &&
+           no_rfsm == o.no_rfsm && no_pscan_prefetch == o.no_pscan_prefetch && cand_density == o.cand_density &&
+           presence_chunk_words == o.presence_chunk_words && lead_switch_bytes == o.lead_switch_bytes &&
+           presence_switch_bytes == o.presence_switch_bytes && presence_after == o.presence_after;
+  }
 };
 
 // Everything pack_query and plan_launch collect about one query.  One Packer per submitting thread is reused from
@@ -2864,6 +2890,7 @@ void PlanEnv::read() {
   presence_chunk_words = cwe && *cwe ? atoi(cwe) : 64;
   lead_switch_bytes = pgpu_lead_switch_bytes();
   presence_switch_bytes = pgpu_presence_switch_bytes();
+  presence_after = ::presence_after();
 }
 
 // A submit's planning scratch beside its Packer: the per-segment analyses with the column views they read, and the
@@ -3867,8 +3894,13 @@ PresenceScratch& presence_scratch() {
 // The launch's tile skip, planned behind plan_launch (the kernel is known only then) and beside the lead decision:
 // which segments would skip with their rows present ("wanted": they count the submit and may trigger the build),
 // and which do skip, their rows being there (DevSeg::skip_*, DevParams::rd_skip).  No HIP call but hipEventQuery.
-void plan_presence(const pgpu_query_desc* q, Packer& pk, DevParams& p, LaunchPlan& pl, SkipInfo* si) {
-  const int after = presence_after();
+// *settled: planning the same query again finds the same answer and does nothing else, as long as the context's
+// plan_epoch stands -- it returned before the submit was counted against any segment's rows, or every candidate
+// segment's rows were seen ready, or every one's declined.  Anything else counts asks, may trigger a build or waits
+// for one, and must be planned per submit.
+void plan_presence(const pgpu_query_desc* q, Packer& pk, DevParams& p, LaunchPlan& pl, SkipInfo* si, bool* settled) {
+  *settled = true;
+  const int after = pk.env.presence_after;
   const int64_t thr = pk.env.presence_switch_bytes;
   if (p.direct != PGPU_KV_RDIRECT || (q->flags & PGPU_Q_EXACT_FILTER_STATS) || after < 0 || thr < 0) return;
   if (!pgpu_rd_skip_ok(p.rd_planes, p.rd_pfx)) return;  // (launches the skip kernel is not built for)
@@ -3898,6 +3930,7 @@ void plan_presence(const pgpu_query_desc* q, Packer& pk, DevParams& p, LaunchPla
   std::vector<int32_t>& wpr = ps.wpr;
   rows.assign((size_t)nseg, nullptr);
   wpr.assign((size_t)nseg, 0);
+  int ncand = 0, nready = 0, ndeclined = 0;
   for (int s = 0; s < nseg; ++s) {
     if (!ch[s].h) continue;
     PresenceState* st = ch[s].h->presence.get();
@@ -3905,7 +3938,11 @@ void plan_presence(const pgpu_query_desc* q, Packer& pk, DevParams& p, LaunchPla
       pl.presence_builds.push_back(ch[s].h->presence);
     rows[s] = presence_ready(*ch[s].h, &wpr[s]);
     if (rows[s]) have += saved[s];
+    ++ncand;
+    nready += rows[s] != nullptr;
+    ndeclined += !rows[s] && st->state.load(std::memory_order_acquire) == PresenceState::kDeclined;
   }
+  *settled = pl.presence_builds.empty() && (nready == ncand || ndeclined == ncand);
   if (!pgpu_lead_switch(have, thr)) return;
   for (int s = 0; s < nseg; ++s) {
     if (!rows[s]) continue;
@@ -3928,11 +3965,15 @@ void plan_presence(const pgpu_query_desc* q, Packer& pk, DevParams& p, LaunchPla
 // launch does not end on it (another condition of try_rdirect fails, PGPU_NO_RDIRECT, the LDS limit), or the lead
 // leaf did not pack as one staged SCAN (kLeadRetry), the query is packed again in query order, so that it runs
 // exactly the plan it would have without the switch.
+// env: the switches to plan under, already read (a prepared submit reads them itself, to compare); null: read here.
+// *settled (optional): see plan_presence.
 int pack_and_plan(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_layout& L, Packer& pk, DevParams& p,
-                  LaunchPlan& pl) {
+                  LaunchPlan& pl, const PlanEnv* given_env = nullptr, bool* settled = nullptr) {
   LeadInfo li;
   PlanEnv env;
-  env.read();  // once per submit; a test that changes a switch between two submits still sees the change
+  // once per submit; a test that changes a switch between two submits still sees the change
+  if (given_env) env = *given_env;
+  else env.read();
   for (int attempt = 0; attempt < 2; ++attempt) {
     pk.clear();
     pk.env = env;
@@ -3953,7 +3994,9 @@ int pack_and_plan(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_
   }
   SkipInfo si;
   const double ts0 = HostTiming::us();
-  plan_presence(q, pk, p, pl, &si);
+  bool presence_settled = true;
+  plan_presence(q, pk, p, pl, &si, &presence_settled);
+  if (settled) *settled = presence_settled;
   host_timing().add(HostTiming::kPresence, ts0, HostTiming::us());
   if (plan_trace_on()) trace_plan(pk, p, pl, li, si);
   return PGPU_OK;
@@ -4247,35 +4290,14 @@ struct LeafWords {
   int64_t raw = 0, mv = 0, inv = 0;
 };
 
-// Turn the packer's offsets into device pointers (bitmaps in the workspace, everything else in the arena), write the
-// arena's host image and point DevParams at its sections
-LeafWords fill_arena(Packer& pk, const ArenaLayout& A, Workspace* ws, const void* dev_table, DevParams& p) {
+// Write the arena's host image and point DevParams at its sections; in the image, the packer's offsets become device
+// pointers (bitmaps in the workspace, everything else in the arena).  The packer itself stays as planned: a prepared
+// query's cached one is shared by every submit.
+LeafWords fill_arena(const Packer& pk, const ArenaLayout& A, Workspace* ws, const void* dev_table, DevParams& p) {
   char* h = (char*)ws->h_arena.p;
   char* d = (char*)ws->arena.p;
   const uint32_t* rawbits = (const uint32_t*)ws->rawbits.p;
   LeafWords w;
-  for (int idx : pk.bits_instrs) pk.instrs[idx].fwd = rawbits + (intptr_t)pk.instrs[idx].fwd;
-  for (DevSeg& sg : pk.segs)
-    for (int k = 0; k < sg.nbits; ++k) sg.bits_w[k] = rawbits + (intptr_t)sg.bits_w[k];
-  for (RawLeaf& r : pk.raws) {
-    r.out = (uint32_t*)rawbits + (intptr_t)r.out;
-    r.vals = (const int64_t*)(d + A.rvals) + (intptr_t)r.vals;
-    w.raw = std::max<int64_t>(w.raw, r.words);
-  }
-  for (MvLeaf& m : pk.mvs) {
-    m.out = (uint32_t*)rawbits + (intptr_t)m.out;
-    m.set = m.set ? (const uint32_t*)(d + A.mvset) + ((intptr_t)m.set - 1) : nullptr;
-    w.mv = std::max<int64_t>(w.mv, m.words);
-  }
-  for (InvLeafX& x : pk.invx) {
-    x.out = (uint32_t*)rawbits + (intptr_t)x.out;
-    x.ids = (const int32_t*)(d + A.invids) + (intptr_t)x.ids;
-    w.inv = std::max<int64_t>(w.inv, x.words);
-  }
-  for (ProgJob& jb : pk.jobs) {
-    jb.out = (uint32_t*)rawbits + (intptr_t)jb.out;
-    for (int k = 0; k < jb.nbits; ++k) jb.bits_w[k] = rawbits + (intptr_t)jb.bits_w[k];
-  }
   memcpy(h + A.mv, pk.mvs.data(), pk.mvs.size() * sizeof(MvLeaf));
   memcpy(h + A.inv, pk.invx.data(), pk.invx.size() * sizeof(InvLeafX));
   memcpy(h + A.jobs, pk.jobs.data(), pk.jobs.size() * sizeof(ProgJob));
@@ -4289,6 +4311,39 @@ LeafWords fill_arena(Packer& pk, const ArenaLayout& A, Workspace* ws, const void
   memcpy(h + A.cols, pk.cols.data(), pk.cols.size() * sizeof(DevColumn));
   memcpy(h + A.pool, pk.pool.data(), pk.pool.size() * 4);
   memcpy(h + A.rem, pk.remaps.data(), pk.remaps.size() * sizeof(void*));
+  // (the image is written, never read: each pointer is computed from the packer's offset)
+  DevInstr* hins = (DevInstr*)(h + A.ins);
+  for (int idx : pk.bits_instrs) hins[idx].fwd = rawbits + (intptr_t)pk.instrs[idx].fwd;
+  DevSeg* hsegs = (DevSeg*)(h + A.segs);
+  for (size_t s = 0; s < pk.segs.size(); ++s)
+    for (int k = 0; k < pk.segs[s].nbits; ++k) hsegs[s].bits_w[k] = rawbits + (intptr_t)pk.segs[s].bits_w[k];
+  RawLeaf* hraws = (RawLeaf*)(h + A.raw);
+  for (size_t i = 0; i < pk.raws.size(); ++i) {
+    const RawLeaf& r = pk.raws[i];
+    hraws[i].out = (uint32_t*)rawbits + (intptr_t)r.out;
+    hraws[i].vals = (const int64_t*)(d + A.rvals) + (intptr_t)r.vals;
+    w.raw = std::max<int64_t>(w.raw, r.words);
+  }
+  MvLeaf* hmvs = (MvLeaf*)(h + A.mv);
+  for (size_t i = 0; i < pk.mvs.size(); ++i) {
+    const MvLeaf& m = pk.mvs[i];
+    hmvs[i].out = (uint32_t*)rawbits + (intptr_t)m.out;
+    hmvs[i].set = m.set ? (const uint32_t*)(d + A.mvset) + ((intptr_t)m.set - 1) : nullptr;
+    w.mv = std::max<int64_t>(w.mv, m.words);
+  }
+  InvLeafX* hinv = (InvLeafX*)(h + A.inv);
+  for (size_t i = 0; i < pk.invx.size(); ++i) {
+    const InvLeafX& x = pk.invx[i];
+    hinv[i].out = (uint32_t*)rawbits + (intptr_t)x.out;
+    hinv[i].ids = (const int32_t*)(d + A.invids) + (intptr_t)x.ids;
+    w.inv = std::max<int64_t>(w.inv, x.words);
+  }
+  ProgJob* hjobs = (ProgJob*)(h + A.jobs);
+  for (size_t i = 0; i < pk.jobs.size(); ++i) {
+    const ProgJob& jb = pk.jobs[i];
+    hjobs[i].out = (uint32_t*)rawbits + (intptr_t)jb.out;
+    for (int k = 0; k < jb.nbits; ++k) hjobs[i].bits_w[k] = rawbits + (intptr_t)jb.bits_w[k];
+  }
   p.segs = (const DevSeg*)(d + A.segs);
   p.instrs = (const DevInstr*)(d + A.ins);
   p.cols = (const DevColumn*)(d + A.cols);
@@ -4306,11 +4361,11 @@ LeafWords fill_arena(Packer& pk, const ArenaLayout& A, Workspace* ws, const void
 // Cancel word in HBM: a query is stopped when the word equals its generation (no reset that could race a cancel
 // issued from another stream); the kernels poll it with uncached loads.  A query already past its deadline is
 // cancelled before it starts (*expired).
-hipError_t arm_cancel(const pgpu_query_desc* q, Workspace* ws, hipStream_t st, DevParams& p, bool* expired) {
+hipError_t arm_cancel(int64_t deadline_ms, Workspace* ws, hipStream_t st, DevParams& p, bool* expired) {
   if (++ws->cancel_gen == 0) ws->cancel_gen = 1;
   p.cancel = (const int32_t*)ws->d_cancel.p;
   p.cancel_gen = ws->cancel_gen;
-  *expired = q->deadline_ms > 0 && now_epoch_ms() >= q->deadline_ms;
+  *expired = deadline_ms > 0 && now_epoch_ms() >= deadline_ms;
   return *expired ? hipMemsetD32Async((hipDeviceptr_t)ws->d_cancel.p, (int)ws->cancel_gen, 1, st) : hipSuccess;
 }
 
@@ -4333,13 +4388,15 @@ bool any_leaf_expanded(const Packer& pk) {
 // Why the query keeps the three launches (prologue, query kernels, finalize), or null: it runs as one.  One launch:
 // a submitted register-direct query with a small table and no kernel before or behind the query kernel.
 // PGPU_Q_SPLIT_LAUNCH (PGPU_SPLIT_LAUNCH=1: every query) keeps the three launches.
+// Of the table's target only what a plan knows before any buffer exists: submitted (TableTarget::tws), exported whole
+// (host_table), eager -- so a prepared query keeps the answer with its plan.
 const char* split_reason(const pgpu_query_desc* q, const pgpu_table_layout& L, const Packer& pk, const DevParams& p,
-                         const LaunchPlan& pl, const TableTarget& t) {
+                         const LaunchPlan& pl, bool submitted, bool exported, bool eager) {
   static const bool env_split = env_flag("PGPU_SPLIT_LAUNCH");
   const uint64_t table_words = pgpu_table_bytes(&L) / 8;
-  if (!t.tws) return "external stream or table";
+  if (!submitted) return "external stream or table";
   if (env_split || (q->flags & PGPU_Q_SPLIT_LAUNCH)) return "forced";
-  if (!t.host_table || t.eager || (q->flags & PGPU_Q_FOLD)) return "table not exported whole";
+  if (!exported || eager || (q->flags & PGPU_Q_FOLD)) return "table not exported whole";
   if (p.direct != PGPU_KV_RDIRECT || p.pscan ||
       !(p.mode == PGPU_MODE_AGG || p.mode == PGPU_MODE_LDS || p.mode == PGPU_MODE_GLOBAL))
     return "not a register-direct AGG / LDS / GLOBAL query";
@@ -4617,8 +4674,8 @@ int64_t pgpu_presence_switch_bytes(void) {
 }
 
 // Every query enters the GPU here, as a sequence of phases: pack_query, drop_reference_replay, plan_launch and
-// split_reason (host only), then pick_stream, ensure_workspace, fill_arena, enqueue_fused or enqueue_split,
-// make_query_handle.
+// split_reason (host only: the plan, launch_impl -- or a prepared query's cached one), then pick_stream,
+// ensure_workspace, fill_arena, enqueue_fused or enqueue_split, make_query_handle (launch_planned).
 // host_table (device-visible pointer into pinned host memory, or null): the finished table is also exported there
 // eager: compact the table (only the best groups by eager_order, when given) on the query's stream right behind
 // its kernels, into the workspace; pgpu_query_collect then only copies the rows out (pgpu_query_submit_ordered)
@@ -4651,27 +4708,17 @@ static void enqueue_presence_builds(pgpu_context* ctx, std::vector<std::shared_p
   builds.clear();
 }
 
-static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream, void* dev_table,
-                       uint64_t table_bytes, int64_t* host_table, pgpu_query** out_query, bool eager = false,
-                       const pgpu_topk* eager_order = nullptr, Workspace* tws = nullptr) {
-  if (!ctx || !q || !out_query) return fail(PGPU_E_INVALID, "null argument");
-  pgpu_table_layout L;
-  int rc = pgpu_table_layout_of(q, &L);
-  if (rc) return rc;
+// Everything behind the plan: what depends on the moment.  pk, pl and split_why are read only (a prepared query's
+// cached plan is shared by concurrent submits); p is this submit's copy, since ensure_workspace, fill_arena and
+// enqueue_fused write the workspace's pointers into it.  builds: the presence builds this submit's plan triggered.
+static int launch_planned(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_table_layout& L, const Packer& pk,
+                          DevParams p, const LaunchPlan& pl, const char* split_why,
+                          std::vector<std::shared_ptr<PresenceState>>& builds, int64_t deadline_ms, void* stream,
+                          TableTarget target, pgpu_query** out_query) {
   const uint64_t need = pgpu_table_bytes(&L);
-  // (tws: the table is tws->table, grown below on the stream the query runs on)
-  if (!tws && (!dev_table || table_bytes < need))
-    return fail(PGPU_E_INVALID, "table buffer %llu bytes < %llu needed", (unsigned long long)table_bytes,
-                (unsigned long long)need);
-  static thread_local Packer tl_packer;  // this thread's submit scratch (see Packer, PlanScratch)
-  Packer& pk = tl_packer;
-  DevParams p;
-  LaunchPlan pl;
-  rc = pack_and_plan(ctx, q, L, pk, p, pl);
-  if (rc) return rc;
-  TableTarget target{dev_table, host_table, eager, eager_order, tws};
-  const char* split_why = split_reason(q, L, pk, p, pl, target);
-
+  Workspace* const tws = target.tws;
+  void* dev_table = target.dev_table;
+  int rc = PGPU_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   {
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -4701,7 +4748,7 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
     host_timing().add(3, tw0, tl0);
     // metadata in and stats (and small tables) out through pinned host memory touched by kernels: no DMA-engine
     // copy sits between two queries' kernels
-    rc = launch_status(arm_cancel(q, ws, st, p, &expired));
+    rc = launch_status(arm_cancel(deadline_ms, ws, st, p, &expired));
     if (!rc)
       rc = split_why ? enqueue_split(ctx, L, pk, pl, A, words, target, split_why, ws, st, p)
                      : enqueue_fused(ctx, L, pl, A.total, target, ws, pick, p, &kernel_is_done);
@@ -4720,10 +4767,11 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
   }
   const hipEvent_t done = kernel_is_done ? pick.ev1 : ws->done;  // (= pick.done)
   const double th0 = HostTiming::us();
-  pgpu_query* qq = make_query_handle(ctx, q, pk, p, pl.grid, ws, st, done, eager);
+  pgpu_query* qq = make_query_handle(ctx, q, pk, p, pl.grid, ws, st, done, target.eager);
+  qq->deadline_ms = deadline_ms;
   host_timing().mark = HostTiming::us();
   host_timing().add(HostTiming::kHandle, th0, host_timing().mark);
-  qq->presence_builds = std::move(pl.presence_builds);
+  qq->presence_builds = std::move(builds);
   qq->ev0 = pick.ev0;
   qq->ev1 = pick.ev1;
   qq->seq = pick.seq;
@@ -4731,6 +4779,29 @@ static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream
   if (expired) qq->stop = PGPU_E_TIMEOUT;
   *out_query = qq;
   return PGPU_OK;
+}
+
+static int launch_impl(pgpu_context* ctx, const pgpu_query_desc* q, void* stream, void* dev_table,
+                       uint64_t table_bytes, int64_t* host_table, pgpu_query** out_query, bool eager = false,
+                       const pgpu_topk* eager_order = nullptr, Workspace* tws = nullptr) {
+  if (!ctx || !q || !out_query) return fail(PGPU_E_INVALID, "null argument");
+  pgpu_table_layout L;
+  int rc = pgpu_table_layout_of(q, &L);
+  if (rc) return rc;
+  const uint64_t need = pgpu_table_bytes(&L);
+  // (tws: the table is tws->table, grown by launch_planned on the stream the query runs on)
+  if (!tws && (!dev_table || table_bytes < need))
+    return fail(PGPU_E_INVALID, "table buffer %llu bytes < %llu needed", (unsigned long long)table_bytes,
+                (unsigned long long)need);
+  static thread_local Packer tl_packer;  // this thread's submit scratch (see Packer, PlanScratch)
+  Packer& pk = tl_packer;
+  DevParams p;
+  LaunchPlan pl;
+  rc = pack_and_plan(ctx, q, L, pk, p, pl);
+  if (rc) return rc;
+  const TableTarget target{dev_table, host_table, eager, eager_order, tws};
+  const char* split_why = split_reason(q, L, pk, p, pl, tws != nullptr, host_table != nullptr, eager);
+  return launch_planned(ctx, q, L, pk, p, pl, split_why, pl.presence_builds, q->deadline_ms, stream, target, out_query);
 }
 
 int pgpu_query_launch(pgpu_context* ctx, const pgpu_query_desc* q, void* stream, void* dev_table,
@@ -5820,6 +5891,60 @@ int plan_expr(const pgpu_query_desc* q, const pgpu_expr_node* expr, int32_t num_
 
 extern "C" {
 
+// What a submit decides from the descriptor, its layout and the trim alone: where the table goes
+struct SubmitShape {
+  uint64_t bytes = 0;
+  // small tables (aggregation only, or up to a few hundred thousand keys) are exported whole into pinned host
+  // memory right behind the kernel and compacted on the host: pgpu_query_collect then synchronises once
+  // (PGPU_Q_FOLD: the table is folded on the device at collect; neither exported nor compacted as it stands)
+  bool folded = false, small = false;
+  // big tables are compacted right behind the kernels on the query stream: the compaction of query i must not
+  // wait in collect() behind query i+1's kernel, which holds every CU (the table stays intact, so a collect with
+  // another order still selects from it)
+  bool ordered = false;
+  bool eager() const { return !small && !folded; }
+};
+static SubmitShape submit_shape(const pgpu_query_desc* q, const pgpu_table_layout& L, const pgpu_topk* order) {
+  SubmitShape sh;
+  sh.bytes = pgpu_table_bytes(&L);
+  sh.folded = (q->flags & PGPU_Q_FOLD) != 0;
+  sh.small = !sh.folded && sh.bytes <= (8u << 20);
+  sh.ordered = order && order->k > 0 && L.num_keys > order->k;
+  return sh;
+}
+
+// The workspace that owns the partial table until pgpu_query_collect (launch_planned grows the table, on the stream it
+// picks for the query), with a small table's pinned host copy
+static int submit_begin(pgpu_context* ctx, const SubmitShape& sh, Workspace** out_tws, void** out_host_table) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIP_TRY(create_query_streams(ctx));  // before the first workspace's stream
+  }
+  int err = 0;
+  Workspace* tws = acquire_ws(ctx, &err);
+  if (!tws) return err;
+  void* h_table_dev = nullptr;
+  if (sh.small) {
+    hipError_t e = tws->h_table.ensure(sh.bytes);
+    if (e == hipSuccess) e = tws->h_table.device_ptr(&h_table_dev);
+    if (e != hipSuccess) {
+      release_ws(ctx, tws);
+      return fail(PGPU_E_HIP, "host table buffer: %s", hipGetErrorString(e));
+    }
+  }
+  *out_tws = tws;
+  *out_host_table = h_table_dev;
+  return PGPU_OK;
+}
+
+static void submit_finish(pgpu_query* qq, Workspace* tws, const pgpu_table_layout& L, const SubmitShape& sh) {
+  qq->tws = tws;
+  qq->layout = L;
+  qq->small = sh.small;
+  qq->eager_ordered = sh.ordered;
+}
+
 static int submit_impl(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_topk* order, pgpu_query** out_query) {
   if (!ctx || !q || !out_query) return fail(PGPU_E_INVALID, "null argument");
   const double t0 = HostTiming::us();
@@ -5827,45 +5952,19 @@ static int submit_impl(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_t
   int rc = pgpu_table_layout_of(q, &L);
   if (rc) return rc;
   host_timing().add(1, t0, HostTiming::us());
-  HIP_TRY(hipSetDevice(ctx->device));
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    HIP_TRY(create_query_streams(ctx));  // before the first workspace's stream
-  }
-  int err = 0;
-  // owns the partial table until pgpu_query_collect (launch_impl grows it, on the stream it picks for the query)
-  Workspace* tws = acquire_ws(ctx, &err);
-  if (!tws) return err;
-  const uint64_t bytes = pgpu_table_bytes(&L);
-  // small tables (aggregation only, or up to a few hundred thousand keys) are exported whole into pinned host
-  // memory right behind the kernel and compacted on the host: pgpu_query_collect then synchronises once
-  // (PGPU_Q_FOLD: the table is folded on the device at collect; neither exported nor compacted as it stands)
-  const bool folded = (q->flags & PGPU_Q_FOLD) != 0;
-  const bool small = !folded && bytes <= (8u << 20);
+  const SubmitShape sh = submit_shape(q, L, order);
+  Workspace* tws = nullptr;
   void* h_table_dev = nullptr;
-  if (small) {
-    hipError_t e = tws->h_table.ensure(bytes);
-    if (e == hipSuccess) e = tws->h_table.device_ptr(&h_table_dev);
-    if (e != hipSuccess) {
-      release_ws(ctx, tws);
-      return fail(PGPU_E_HIP, "host table buffer: %s", hipGetErrorString(e));
-    }
-  }
+  rc = submit_begin(ctx, sh, &tws, &h_table_dev);
+  if (rc) return rc;
   pgpu_query* qq = nullptr;
-  // big tables are compacted right behind the kernels on the query stream: the compaction of query i must not
-  // wait in collect() behind query i+1's kernel, which holds every CU (the table stays intact, so a collect with
-  // another order still selects from it)
-  const bool ordered = order && order->k > 0 && L.num_keys > order->k;
-  rc = launch_impl(ctx, q, nullptr, nullptr, 0, (int64_t*)h_table_dev, &qq, !small && !folded,
-                   ordered ? order : nullptr, tws);
+  rc = launch_impl(ctx, q, nullptr, nullptr, 0, (int64_t*)h_table_dev, &qq, sh.eager(), sh.ordered ? order : nullptr,
+                   tws);
   if (rc) {
     release_ws(ctx, tws);
     return rc;
   }
-  qq->tws = tws;
-  qq->layout = L;
-  qq->small = small;
-  qq->eager_ordered = ordered;
+  submit_finish(qq, tws, L, sh);
   *out_query = qq;
   return PGPU_OK;
 }
@@ -5988,5 +6087,325 @@ int pgpu_query_execute(pgpu_context* ctx, const pgpu_query_desc* q, int64_t* out
   if (rc) return rc;
   return pgpu_query_collect(qq, out_keys, out_cells, capacity, out_num_groups, out_stats);
 }
+
+
+// ---- prepared queries: plan once, submit many times ---------------------------------------------------------------
+namespace {
+
+// Everything a descriptor, an expression and a trim point to, copied: no caller memory is read after the prepare.
+// Copied as given -- a null pointer stays null, a count stays what it was -- so that planning the copy refuses what
+// planning the original would refuse, with the same message.
+struct OwnedDesc {
+  pgpu_query_desc q{};
+  std::vector<pgpu_segment_plan> plans;
+  std::vector<int32_t> column_maps, ids, gcols, gcards, sum_exp, sum_parts, order_cards;
+  std::vector<pgpu_filter_node> nodes;
+  std::vector<int64_t> values;  // raw leaves' values: 8 bytes each, int64 or double bits
+  std::vector<const pgpu_buffer*> remaps;
+  std::vector<pgpu_agg> aggs;
+  std::vector<pgpu_expr_node> expr;
+  std::vector<pgpu_literal> lits;
+  bool has_expr = false, has_order = false;
+  int32_t num_nodes = 0;
+  pgpu_topk order{};
+
+  static size_t cnt(int64_t n) { return (size_t)std::max<int64_t>(0, n); }
+  void copy(const pgpu_query_desc* d, const pgpu_expr_node* x, int32_t nx, const pgpu_topk* o) {
+    q = *d;
+    const size_t nseg = d->segments ? cnt(d->num_segments) : 0, ncols = cnt(d->num_columns);
+    const size_t ngc = cnt(d->num_group_columns), nagg = cnt(d->num_aggs);
+    auto ints = [](std::vector<int32_t>& v, const int32_t* src, size_t n) -> const int32_t* {
+      if (!src) return nullptr;
+      v.assign(src, src + n);
+      if (v.empty()) v.push_back(0);  // (a non-null pointer stays one)
+      return v.data();
+    };
+    if (d->aggs) aggs.assign(d->aggs, d->aggs + nagg);
+    q.aggs = d->aggs ? (aggs.empty() ? (aggs.push_back(pgpu_agg{}), aggs.data()) : aggs.data()) : nullptr;
+    q.group_columns = ints(gcols, d->group_columns, ngc);
+    q.group_cardinalities = ints(gcards, d->group_cardinalities, ngc);
+    q.sum_exp = ints(sum_exp, d->sum_exp, nagg);
+    q.sum_parts = ints(sum_parts, d->sum_parts, nagg);
+    has_expr = x != nullptr;
+    num_nodes = nx;
+    // sizes first: none of the pools may move once pointers into it are handed out
+    size_t nnodes = 0, nids = 0, nvals = 0, nmaps = 0, nrem = 0;
+    auto ids_of = [](const pgpu_filter_node& nd) -> size_t {
+      if (!nd.ids || nd.num_ids <= 0) return 0;
+      if (nd.op == PGPU_F_SORTED) return 2 * (size_t)nd.num_ids;
+      return nd.op == PGPU_F_SCAN || nd.op == PGPU_F_INVERTED ? (size_t)nd.num_ids : 0;
+    };
+    auto vals_of = [](const pgpu_filter_node& nd) -> size_t {
+      if (!nd.values || (nd.op != PGPU_F_RAW_SCAN && nd.op != PGPU_F_RANGE_INDEX)) return 0;
+      return nd.pred == PGPU_PRED_SET ? cnt(nd.num_ids) : 2;
+    };
+    for (size_t s = 0; s < nseg; ++s) {
+      const pgpu_segment_plan& sp = d->segments[s];
+      if (sp.column_map) nmaps += ncols;
+      if (sp.group_remap) nrem += ngc;
+      if (has_expr || !sp.filter) continue;
+      nnodes += cnt(sp.num_filter_nodes);
+      for (size_t i = 0; i < cnt(sp.num_filter_nodes); ++i) nids += ids_of(sp.filter[i]), nvals += vals_of(sp.filter[i]);
+    }
+    column_maps.reserve(nmaps + 1);
+    remaps.reserve(nrem + 1);
+    nodes.reserve(nnodes + 1);
+    ids.reserve(nids + 1);
+    values.reserve(nvals + 1);
+    if (d->segments) plans.assign(d->segments, d->segments + nseg);
+    for (size_t s = 0; s < nseg; ++s) {
+      pgpu_segment_plan& sp = plans[s];
+      if (sp.column_map) {
+        const int32_t* src = sp.column_map;
+        sp.column_map = column_maps.data() + column_maps.size();
+        column_maps.insert(column_maps.end(), src, src + ncols);
+      }
+      if (sp.group_remap) {
+        const pgpu_buffer* const* src = sp.group_remap;
+        sp.group_remap = remaps.data() + remaps.size();
+        remaps.insert(remaps.end(), src, src + ngc);
+      }
+      if (has_expr) {  // (segments[i].filter is ignored beside an expression)
+        sp.filter = nullptr;
+        sp.num_filter_nodes = 0;
+        continue;
+      }
+      if (!sp.filter) continue;
+      const pgpu_filter_node* src = sp.filter;
+      const size_t n = cnt(sp.num_filter_nodes);
+      sp.filter = nodes.data() + nodes.size();
+      for (size_t i = 0; i < n; ++i) {
+        pgpu_filter_node nd = src[i];
+        if (const size_t k = ids_of(nd)) {
+          const int32_t* from = nd.ids;
+          nd.ids = ids.data() + ids.size();
+          ids.insert(ids.end(), from, from + k);
+        }
+        if (const size_t k = vals_of(nd)) {
+          const int64_t* at = values.data() + values.size();
+          values.resize(values.size() + k);
+          memcpy((void*)at, nd.values, 8 * k);
+          nd.values = at;
+        }
+        nodes.push_back(nd);
+      }
+    }
+    q.segments = d->segments ? plans.data() : nullptr;
+    if (has_expr) {
+      const size_t n = cnt(nx);
+      expr.assign(x, x + n);
+      size_t nl = 0;
+      for (const pgpu_expr_node& e : expr) nl += e.values ? cnt(e.num_values) : 0;
+      lits.reserve(nl + 1);
+      for (pgpu_expr_node& e : expr) {
+        if (!e.values) continue;
+        const pgpu_literal* from = e.values;
+        e.values = lits.data() + lits.size();
+        lits.insert(lits.end(), from, from + cnt(e.num_values));
+      }
+      if (expr.empty()) expr.push_back(pgpu_expr_node{});  // (zero nodes: still "an expression was given")
+    }
+    has_order = o != nullptr;
+    if (o) {
+      order = *o;
+      order.group_cardinalities = ints(order_cards, o->group_cardinalities, cnt(o->num_group_columns));
+    }
+  }
+  const pgpu_expr_node* expr_ptr() const { return has_expr ? expr.data() : nullptr; }
+  const pgpu_topk* order_ptr() const { return has_order ? &order : nullptr; }
+};
+
+// One plan of a prepared query: what launch_impl derives before it touches a workspace.  Immutable once published
+// (pgpu_prepared::plan); launch_planned reads it const from any number of threads.
+struct PreparedPlan {
+  std::shared_ptr<const OwnedDesc> owned;  // what pd.q's and the expression's pointers lead to
+  PlannedDesc pd;                          // with an expression: the planned descriptor (pd.q)
+  pgpu_table_layout L{};
+  SubmitShape shape;
+  Packer pk;        // (pk.env: the switches it was planned under)
+  DevParams p{};    // as pack_and_plan left them: copied per submit
+  LaunchPlan pl;
+  const char* split_why = nullptr;
+  uint64_t epoch = 0;    // pgpu_context::plan_epoch read before planning began
+  bool settled = false;  // plan_presence
+  const pgpu_query_desc* desc() const { return owned->has_expr ? &pd.q : &owned->q; }
+};
+
+std::atomic<int64_t> g_prepared_live{0};
+
+}  // namespace
+
+struct pgpu_prepared {
+  pgpu_context* ctx = nullptr;
+  std::shared_ptr<const OwnedDesc> owned;
+  std::mutex mu;                             // guards `plan`
+  std::shared_ptr<const PreparedPlan> plan;  // the cached plan, or null: the next submit plans
+  std::atomic<int64_t> plans{0}, hits{0}, uncached{0};
+  std::atomic<bool> fresh{true};  // `plan` is pgpu_query_prepare's own and no submit has used it yet
+};
+
+namespace {
+
+// Plan the owned descriptor from scratch under `env`, exactly as pgpu_query_submit_ordered plans the caller's: every
+// error it would return comes from here, with its message.
+int plan_prepared(pgpu_context* ctx, const std::shared_ptr<const OwnedDesc>& owned, const PlanEnv& env, uint64_t epoch,
+                  PreparedPlan& out) {
+  out.owned = owned;
+  out.epoch = epoch;
+  if (owned->has_expr) {
+    const double t0 = HostTiming::us();
+    const int rc = plan_expr(&owned->q, owned->expr_ptr(), owned->num_nodes, out.pd);
+    if (rc) return rc;
+    host_timing().add(0, t0, HostTiming::us());
+  }
+  const pgpu_query_desc* q = out.desc();
+  const double t1 = HostTiming::us();
+  int rc = pgpu_table_layout_of(q, &out.L);
+  if (rc) return rc;
+  host_timing().add(1, t1, HostTiming::us());
+  out.shape = submit_shape(q, out.L, owned->order_ptr());
+  rc = pack_and_plan(ctx, q, out.L, out.pk, out.p, out.pl, &env, &out.settled);
+  if (rc) return rc;
+  out.split_why = split_reason(q, out.L, out.pk, out.p, out.pl, true, out.shape.small, out.shape.eager());
+  return PGPU_OK;
+}
+
+// The submit behind a plan: workspace for the table, launch, handle
+int submit_prepared(pgpu_context* ctx, const PreparedPlan& pp, std::vector<std::shared_ptr<PresenceState>>& builds,
+                    int64_t deadline_ms, uint8_t* matched_out, pgpu_query** out_query) {
+  Workspace* tws = nullptr;
+  void* h_table_dev = nullptr;
+  int rc = submit_begin(ctx, pp.shape, &tws, &h_table_dev);
+  if (rc) return rc;
+  pgpu_query* qq = nullptr;
+  const TableTarget target{nullptr, (int64_t*)h_table_dev, pp.shape.eager(),
+                           pp.shape.ordered ? pp.owned->order_ptr() : nullptr, tws};
+  rc = launch_planned(ctx, pp.desc(), pp.L, pp.pk, pp.p, pp.pl, pp.split_why, builds, deadline_ms, nullptr, target, &qq);
+  if (rc) {
+    release_ws(ctx, tws);
+    return rc;
+  }
+  submit_finish(qq, tws, pp.L, pp.shape);
+  qq->matched_out = matched_out;
+  *out_query = qq;
+  return PGPU_OK;
+}
+
+}  // namespace
+
+int pgpu_query_prepare(pgpu_context* ctx, const pgpu_query_desc* q, const pgpu_expr_node* expr, int32_t num_nodes,
+                       const pgpu_topk* order, pgpu_prepared** out) {
+  if (!ctx || !q || !out) return fail(PGPU_E_INVALID, "null argument");
+  if (expr && num_nodes < 0) return fail(PGPU_E_INVALID, "null argument");  // (plan_expr's check, before the copy)
+  auto owned = std::make_shared<OwnedDesc>();
+  owned->copy(q, expr, num_nodes, order);
+  // planned once here, so that what cannot be planned is refused here.  This plan is the first submit's
+  // (pgpu_prepared::fresh): where planning counts an ask for presence rows or prints the trace, it has done so once,
+  // as the first plain submit would have.
+  PlanEnv env;
+  env.read();
+  const uint64_t epoch = ctx->plan_epoch.load();
+  auto pp = std::make_shared<PreparedPlan>();
+  const int rc = plan_prepared(ctx, owned, env, epoch, *pp);
+  if (rc) return rc;
+  auto* h = new pgpu_prepared();
+  h->ctx = ctx;
+  h->owned = owned;
+  h->plan = pp;
+  h->plans = 1;
+  g_prepared_live.fetch_add(1);
+  *out = h;
+  return PGPU_OK;
+}
+
+int pgpu_prepared_submit(pgpu_prepared* h, int64_t deadline_ms, uint8_t* matched_out, int32_t num_segments,
+                         pgpu_query** out_query) {
+  if (!h || !out_query) return fail(PGPU_E_INVALID, "null argument");
+  if (matched_out && num_segments != h->owned->q.num_segments)
+    return fail(PGPU_E_INVALID, "matched-segment flags: %d entries for a %d-segment query", num_segments,
+                h->owned->q.num_segments);
+  pgpu_context* ctx = h->ctx;
+  HostTiming& ht = host_timing();
+  const double t0 = HostTiming::us();
+  ht.mark = 0;
+  PlanEnv env;
+  env.read();  // per submit: a switch changed between two submits plans again
+  const uint64_t epoch = ctx->plan_epoch.load();
+  std::shared_ptr<const PreparedPlan> pp;
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    pp = h->plan;
+  }
+  int rc;
+  std::vector<std::shared_ptr<PresenceState>> builds;
+  // a cached plan is used only where a fresh one would be the same plan: same switches, nothing the planners read
+  // changed since (plan_epoch), and nothing that a plan does beside planning (presence asks: `settled`; the trace)
+  const bool trace = plan_trace_on();
+  const bool same = pp && pp->epoch == epoch && pp->pk.env == env;
+  if (same && h->fresh.exchange(false)) {
+    // pgpu_query_prepare's own plan: this submit's, as if it had planned it itself (its presence asks were counted
+    // and its trace lines printed at the prepare, once).  It stays published only if a later submit may use it.
+    if (!pp->settled || trace) {
+      std::lock_guard<std::mutex> lk(h->mu);
+      if (h->plan == pp) h->plan = nullptr;
+      h->uncached.fetch_add(1);
+    }
+    builds = pp->pl.presence_builds;
+    rc = submit_prepared(ctx, *pp, builds, deadline_ms, matched_out, out_query);
+  } else if (same && pp->settled && !trace) {
+    h->hits.fetch_add(1);
+    if (ht.on()) ++ht.cached;
+    rc = submit_prepared(ctx, *pp, builds, deadline_ms, matched_out, out_query);
+  } else {
+    // planned into this thread's scratch, as the plain path plans into its own; a settled plan is moved out of it
+    // and published, anything else serves this submit alone
+    h->fresh.store(false);
+    static thread_local PreparedPlan scratch;
+    rc = plan_prepared(ctx, h->owned, env, epoch, scratch);
+    if (!rc) {
+      h->plans.fetch_add(1);
+      if (scratch.settled && !trace) {
+        auto np = std::make_shared<PreparedPlan>(std::move(scratch));
+        {
+          std::lock_guard<std::mutex> lk(h->mu);
+          h->plan = np;
+        }
+        rc = submit_prepared(ctx, *np, builds, deadline_ms, matched_out, out_query);
+      } else {
+        {
+          std::lock_guard<std::mutex> lk(h->mu);
+          h->plan = nullptr;
+        }
+        h->uncached.fetch_add(1);
+        builds = std::move(scratch.pl.presence_builds);
+        rc = submit_prepared(ctx, scratch, builds, deadline_ms, matched_out, out_query);
+      }
+    }
+    scratch.owned.reset();  // (the scratch keeps its storage, not the query)
+  }
+  const double t1 = HostTiming::us();
+  if (ht.on()) ++ht.prepared;
+  if (ht.mark > 0) ht.add(HostTiming::kTeardown, ht.mark, t1);
+  ht.add(5, t0, t1);
+  ht.done();
+  return rc;
+}
+
+int pgpu_prepared_counts(const pgpu_prepared* h, struct pgpu_prepared_counts* out) {
+  if (!h || !out) return fail(PGPU_E_INVALID, "null argument");
+  out->plans = h->plans.load();
+  out->hits = h->hits.load();
+  out->uncached = h->uncached.load();
+  return PGPU_OK;
+}
+
+int pgpu_prepared_release(pgpu_prepared* h) {
+  if (!h) return PGPU_OK;
+  g_prepared_live.fetch_sub(1);
+  delete h;
+  return PGPU_OK;
+}
+
+int64_t pgpu_prepared_live(void) { return g_prepared_live.load(); }
 
 }  // extern "C"

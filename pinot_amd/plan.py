@@ -551,7 +551,9 @@ class GpuPlanMaker:
         self._desc_static: Dict[tuple, tuple] = {}  # (segment uids, columns, views) -> (column maps, handles)
         # prepared submissions: the same query object over the same segments with the same options re-submitted
         # (a dashboard's repeated query) reuses its filter program, descriptor and trim -- only the deadline is
-        # restamped.  Dropped whenever a global dictionary or a segment it names changes.
+        # restamped -- and, inside the library, its plan (pgpu_query_prepare / pgpu_prepared_submit; each entry owns
+        # its native handle, released with the entry).  Dropped whenever a global dictionary or a segment it names
+        # changes.
         self._prepared: Dict[tuple, tuple] = {}
         self._distinct: Dict[int, tuple] = {}  # id(query) -> (query, its DISTINCTCOUNT passes)
         if hasattr(ctx, "add_listener"):
@@ -854,20 +856,19 @@ class GpuPlanMaker:
         order = None if lowered else self.trim_order(query, globals_)
         if len(self._prepared) >= 32:
             self._prepared.clear()
-        hit = self._prepared[pkey] = (query, expr, desc, keep, globals_, L, order)
+        # (the last entry: the library's own prepared query, made at the entry's first launch and released with it)
+        hit = self._prepared[pkey] = (query, expr, desc, keep, globals_, L, order, _lib.PreparedQuery())
         return hit
 
     def _launch(self, prepared: tuple, segments: Sequence[GpuSegment]) -> "PendingQuery":
-        query, expr, desc, keep, globals_, L, order = prepared
-        h = C.c_void_p()
-        _lib.check(self.ctx._lib.pgpu_query_submit_ordered(
-            self.ctx.handle, C.byref(desc), expr[0] if expr is not None else None, expr[1] if expr is not None else 0,
-            C.byref(order) if order is not None else None, C.byref(h)))
+        query, expr, desc, keep, globals_, L, order, native = prepared
+        matched = np.zeros(max(1, len(segments)), dtype=np.uint8)
+        # one call: planned once per prepared entry inside the library (pgpu_query_prepare), submitted with this
+        # submit's deadline and matched-segments buffer (pgpu_prepared_submit)
+        h = native.submit(self.ctx.handle, desc, expr, order, matched, len(segments))
         pq = PendingQuery(self, query, len(segments), h, L, globals_)
         pq.order = order
-        pq.matched = np.zeros(max(1, len(segments)), dtype=np.uint8)
-        _lib.check(self.ctx._lib.pgpu_query_matched_segments(h, pq.matched.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                             len(segments)))
+        pq.matched = matched
         return pq
 
     # -- DISTINCTCOUNT (pinot_amd/distinct.py) --

@@ -1,5 +1,7 @@
 """Host-side cost of one query, by phase (GPU box): filter_expr, build_desc, table layout, the submit call, the
-collect call and the finish -- each timed over many repetitions of a bench workload's query on small segments.
+collect call and the finish -- each timed over many repetitions of a bench workload's query on small segments, planned
+from scratch each time (pgpu_query_submit_ordered); then the same query through GpuPlanMaker.submit / collect, whose
+re-submissions go through the library's prepared query (pgpu_prepared_submit).
 
     python tools/hostprof.py [workload] [segments] [docs] [reps]
 """
@@ -64,6 +66,18 @@ def main():
     print(f"{name}: {nseg} segments x {docs} docs, {reps} queries, us per query:")
     for k, v in t.items():
         print(f"  {k:12s} {1e6 * v / reps:8.1f}")
+    # the same query the way callers submit it: GpuPlanMaker's prepared submissions (one library call per submit)
+    ts = tc = 0.0
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        pq = pm.submit(q, segs)
+        t1 = time.perf_counter()
+        pm.collect(pq)
+        t2 = time.perf_counter()
+        ts += t1 - t0
+        tc += t2 - t1
+    print(f"  pm.submit    {1e6 * ts / reps:8.1f}")
+    print(f"  pm.collect   {1e6 * tc / reps:8.1f}")
     for s in segs:
         s.release()
 
