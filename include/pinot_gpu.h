@@ -655,6 +655,47 @@ int pgpu_query_collect_mode(pgpu_query* query, uint64_t inner_keys, const double
                             int64_t* out_keys, int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
                             pgpu_query_stats* out_stats, pgpu_table_layout* out_layout);
 
+/* ---- Value runs: the mergeable intermediates of DISTINCTCOUNT, PERCENTILE and MODE -------------------------------
+ * A server never returns a final value of these functions: the broker merges the value set
+ * (DistinctCountAggregationFunction.java:252-310), the value list (PercentileAggregationFunction.java:82-100) and the
+ * value -> count map (ModeAggregationFunction.java:416-456) across servers.  Section 0 of the table GROUP BY g_1..g_n,
+ * c -- count(g, cid), key = g + inner * cid -- is all three at once, and comes back as a CSR over the inner keys g:
+ *   offsets  uint64[inner_keys + 1]  offsets[g] = the occupied cells (g', cid) with g' < g; offsets[inner_keys] = the
+ *                                    total number of runs
+ *   cids     uint32[total]           elements offsets[g] .. offsets[g + 1]: the occupied cid of g, strictly ascending
+ *   counts   int64[total]            their section-0 counts
+ * A cell is occupied when its count > 0 (the fold's and the selection's test), so offsets[g + 1] - offsets[g] equals
+ * the fold's distinct-count section cell for cell.  Every element has one writer and the result does not depend on
+ * scheduling.
+ * pgpu_table_runs enqueues that on `stream` without synchronising, for dense and one-word hash input as
+ * pgpu_table_fold takes them; the temporary memory comes from the context's pool in stream order.  dev_offsets is
+ * always written in full; elements of dev_cids / dev_counts with an index >= run_capacity are not written, and nothing
+ * is stored outside the three arrays whatever the table holds.  It is the call a multi-GPU combine makes on its
+ * reduced table, next to pgpu_table_fold.
+ * Precondition: every cid is below 2^32 (an id of a global dictionary is an int32), i.e. no occupied key of the table
+ * is inner_keys * 2^32 or more.  An occupied hash slot with a larger key cannot be packed for the sort and is left out,
+ * so that for such a table the offsets no longer add up to the fold's distinct counts; a dense table of that size
+ * would have its cid truncated to 32 bits.  Every table the runtime builds meets it.
+ *   PGPU_E_INVALID / PGPU_E_UNSUPPORTED: as pgpu_fold_layout_of; PGPU_E_INVALID for a NULL output */
+int pgpu_table_runs(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
+                    uint64_t inner_keys, void* dev_offsets, void* dev_cids, void* dev_counts, uint64_t run_capacity);
+/* pgpu_query_collect_fold plus the value runs of the returned rows, for a query submitted with PGPU_Q_FOLD: waits
+ * (PGPU_E_CANCELLED / PGPU_E_TIMEOUT pass through with nothing folded), folds, counts the runs and reads their number
+ * back, compacts every non-empty key of the folded table ascending by g (out_keys, out_cells = capacity x folded
+ * num_sections) and emits the runs: out_offsets[i] .. out_offsets[i + 1] of out_cids / out_counts belong to row i, and
+ * out_offsets has *out_num_groups + 1 entries (so capacity + 1 are needed).  There is no `order`: the server-side
+ * ORDER BY trim is not applied to a value-set result -- the broker's reduce over a superset of the trimmed rows gives
+ * the same answer.
+ * When capacity or run_capacity is too small the call returns PGPU_E_INVALID with the needed counts in *out_num_groups
+ * and *out_num_runs, writes no rows or runs and KEEPS the query: call again with larger buffers, or call
+ * pgpu_query_release.  Every other outcome releases the query, as pgpu_query_collect_fold does -- a NULL
+ * out_num_groups or out_num_runs included (PGPU_E_INVALID); only a NULL query, or one that was never submitted, has
+ * nothing to release. */
+int pgpu_query_collect_runs(pgpu_query* query, uint64_t inner_keys, int64_t* out_keys, int64_t* out_cells,
+                            uint64_t capacity, uint64_t* out_num_groups, uint64_t* out_offsets, uint32_t* out_cids,
+                            int64_t* out_counts, uint64_t run_capacity, uint64_t* out_num_runs,
+                            pgpu_query_stats* out_stats, pgpu_table_layout* out_layout);
+
 /* Single-GPU asynchronous form (the combine operator of one server: BaseCombineOperator.getNextBlock submits the
  * segments' work and blocks in mergeResults, core/operator/combine/BaseCombineOperator.java:79-146):
  *   pgpu_query_submit  packs the plan, enqueues the query on a context-owned stream with its own partial table

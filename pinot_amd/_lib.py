@@ -265,6 +265,11 @@ SIGNATURES = [
                                           C.POINTER(C.c_double), C.c_uint64, C.POINTER(TopK), C.POINTER(C.c_int64),
                                           C.POINTER(C.c_int64), C.c_uint64, C.POINTER(C.c_uint64),
                                           C.POINTER(QueryStats), C.POINTER(TableLayout)]),
+    ("pgpu_table_runs", C.c_int, [_P, C.POINTER(TableLayout), _P, _P, C.c_uint64, _P, _P, _P, C.c_uint64]),
+    ("pgpu_query_collect_runs", C.c_int, [_P, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_uint64,
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                          C.POINTER(C.c_int64), C.c_uint64, C.POINTER(C.c_uint64),
+                                          C.POINTER(QueryStats), C.POINTER(TableLayout)]),
     ("pgpu_query_submit", C.c_int, [_P, C.POINTER(QueryDesc), C.POINTER(_P)]),
     ("pgpu_query_collect", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_uint64,
                                      C.POINTER(C.c_uint64), C.POINTER(QueryStats)]),

@@ -84,6 +84,13 @@ size_t pgpu_mode_temp_bytes(uint64_t N, bool hash, uint64_t inner, bool avg, int
 hipError_t pgpu_launch_mode(const int64_t* in, uint64_t N, int32_t nsec, bool hash, uint64_t inner, const double* values,
                             uint64_t num_values, bool avg, int64_t* mode, void* temp, size_t temp_bytes, int num_cus,
                             hipStream_t st);
+// value runs of the same table: the count (offsets), then the emit (cids, counts) (pgpu_runs.hip)
+size_t pgpu_runs_temp_bytes(uint64_t N, bool hash, uint64_t inner, int num_cus);
+hipError_t pgpu_launch_runs_count(const int64_t* in, uint64_t N, int32_t nsec, bool hash, uint64_t inner,
+                                  uint64_t* offsets, void* temp, size_t temp_bytes, int num_cus, hipStream_t st);
+hipError_t pgpu_launch_runs_emit(const int64_t* in, uint64_t N, int32_t nsec, bool hash, uint64_t inner,
+                                 const uint64_t* offsets, uint32_t* cids, int64_t* counts, uint64_t cap, void* temp,
+                                 size_t temp_bytes, int num_cus, hipStream_t st);
 
 namespace {
 
@@ -333,6 +340,8 @@ struct Workspace {
   DevMem fold_tmp;                     // ... the selection's, then the mode reduction's temporary behind it: one
                                        // buffer, since the two stages are ordered on the one stream
   DevMem mode_vals;                    // pgpu_query_collect_mode: the column's values
+  DevMem runs_off, runs_cids, runs_counts;  // pgpu_query_collect_runs: the value runs of the query's table
+  PinnedMem h_runs_total;              // ... their number, read between the count and the emit
   PinnedMem h_arena, h_stats, h_total, h_table, h_segcnt, h_leafbits, h_segany, h_fsment;
   PinnedMem h_fold;                    // pgpu_query_collect_fold: a small folded table, compacted on the host
   PinnedMem h_mode_vals;               // pgpu_query_collect_mode: the caller's values, staged for the copy to mode_vals
@@ -5208,15 +5217,16 @@ int pgpu_table_topk(pgpu_context* ctx, const pgpu_table_layout* layout, const vo
 }  // extern "C"
 
 // ---- DISTINCTCOUNT, PERCENTILE, MODE: the fold of a GROUP BY g, c table over c, the rank selection and the mode -----
-// reduction behind it (include/pinot_gpu.h; kernels in pgpu_fold.hip, pgpu_select.hip, pgpu_mode.hip).  The nine entry
-// points state what they were asked for as a FoldedSpec and share one layout builder (folded_layout), one size of
-// temporary memory (folded_temp_bytes) and one enqueue (enqueue_folded).
+// reduction behind it, or the value runs of the table beside it (include/pinot_gpu.h; kernels in pgpu_fold.hip,
+// pgpu_select.hip, pgpu_mode.hip, pgpu_runs.hip).  The eleven entry points state what they were asked for as a
+// FoldedSpec and share one layout builder (folded_layout), one size of temporary memory (folded_temp_bytes) and one
+// enqueue (enqueue_folded).
 namespace {
 
 // Which public contract is served: the stage names the last step asked for, not what the numbers happen to be -- a
 // selection of 0 percentiles or a mode reduction with an empty mask is refused as such, never run as the step before.
-enum FoldedStage { STAGE_FOLD, STAGE_SELECT, STAGE_MODE };
-const char* const kStageTable[] = {"folded", "selected", "mode"};
+enum FoldedStage { STAGE_FOLD, STAGE_SELECT, STAGE_MODE, STAGE_RUNS };
+const char* const kStageTable[] = {"folded", "selected", "mode", "runs"};
 
 struct FoldedSpec {
   FoldedStage stage = STAGE_FOLD;
@@ -5227,10 +5237,12 @@ struct FoldedSpec {
   const double* values = nullptr;       // PGPU_MODE_AVG: the column's values ...
   uint64_t num_values = 0;
   bool values_on_device = false;        // ... in device memory (the table functions) or the caller's host memory
+  uint64_t* run_offsets = nullptr;      // STAGE_RUNS: uint64[inner_keys + 1] in device memory, written by the count
 
   bool selects() const { return stage == STAGE_SELECT || (stage == STAGE_MODE && num_percentiles != 0); }
   bool modes() const { return stage == STAGE_MODE; }
   bool avg() const { return modes() && (reducers & PGPU_MODE_AVG) != 0; }
+  bool runs() const { return stage == STAGE_RUNS; }  // (its table is the folded one: nothing is appended to it)
 };
 
 // The layout of the resulting table and where the stages write in it: sections [0, picks_at - 1) are the input's,
@@ -5339,19 +5351,28 @@ size_t folded_temp_bytes(const pgpu_table_layout& in, const FoldedSpec& s, int n
   size_t tb = 0;
   if (s.selects()) tb = std::max(tb, pgpu_select_temp_bytes(in.num_keys, hash, s.inner_keys, num_cus));
   if (s.modes()) tb = std::max(tb, pgpu_mode_temp_bytes(in.num_keys, hash, s.inner_keys, s.avg(), num_cus));
+  if (s.runs()) tb = std::max(tb, pgpu_runs_temp_bytes(in.num_keys, hash, s.inner_keys, num_cus));
   return tb;
 }
 
 // The device work of every folded entry point, on `st`: the fold of `table` (layout `in`) into `out` (layout
 // fl.layout), then the selection and the mode reduction of `s` into their sections of `out`.  `s` and `fl` have passed
-// folded_layout and check_operands; s.values are in device memory; temp holds folded_temp_bytes(...) bytes.
+// folded_layout and check_operands; s.values are in device memory; temp holds folded_temp_bytes(...) bytes.  The runs
+// stage enqueues its count only (s.run_offsets) and leaves `temp` as enqueue_runs_emit needs it; `out` = nullptr then
+// skips the fold (pgpu_table_runs has no folded table to write).
 int enqueue_folded(const pgpu_table_layout& in, const void* table, const FoldedSpec& s, const FoldedLayout& fl,
                    void* out, void* temp, size_t temp_bytes, int num_cus, hipStream_t st) {
   const int64_t* t = (const int64_t*)table;
   int64_t* o = (int64_t*)out;
   const bool hash = in.key_kind == PGPU_KEYS_HASH;
-  hipError_t e = pgpu_launch_fold(t, in.num_keys, in.num_sections, in.section_op, hash, s.inner_keys, o, num_cus, st);
+  hipError_t e = hipSuccess;
+  if (o) e = pgpu_launch_fold(t, in.num_keys, in.num_sections, in.section_op, hash, s.inner_keys, o, num_cus, st);
   if (e != hipSuccess) return fail(PGPU_E_HIP, "table fold: %s", hipGetErrorString(e));
+  if (s.runs()) {
+    e = pgpu_launch_runs_count(t, in.num_keys, in.num_sections, hash, s.inner_keys, s.run_offsets, temp, temp_bytes,
+                               num_cus, st);
+    if (e != hipSuccess) return fail(PGPU_E_HIP, "table runs: %s", hipGetErrorString(e));
+  }
   if (s.selects()) {
     e = pgpu_launch_select(t, in.num_keys, in.num_sections, hash, s.inner_keys, s.percentiles, s.num_percentiles, o,
                            o + (uint64_t)fl.picks_at * s.inner_keys, temp, temp_bytes, num_cus, st);
@@ -5364,6 +5385,15 @@ int enqueue_folded(const pgpu_table_layout& in, const void* table, const FoldedS
     if (e != hipSuccess) return fail(PGPU_E_HIP, "table mode: %s", hipGetErrorString(e));
   }
   return PGPU_OK;
+}
+
+// The second half of the runs stage, behind enqueue_folded on `st` with the same `temp`: the runs below `cap`.
+int enqueue_runs_emit(const pgpu_table_layout& in, const void* table, const FoldedSpec& s, void* cids, void* counts,
+                      uint64_t cap, void* temp, size_t temp_bytes, int num_cus, hipStream_t st) {
+  const hipError_t e = pgpu_launch_runs_emit((const int64_t*)table, in.num_keys, in.num_sections,
+                                             in.key_kind == PGPU_KEYS_HASH, s.inner_keys, s.run_offsets,
+                                             (uint32_t*)cids, (int64_t*)counts, cap, temp, temp_bytes, num_cus, st);
+  return e == hipSuccess ? PGPU_OK : fail(PGPU_E_HIP, "table runs: %s", hipGetErrorString(e));
 }
 
 // pgpu_table_fold, pgpu_table_select, pgpu_table_mode: caller-owned memory, nothing waits for the kernels.
@@ -5392,6 +5422,69 @@ int table_folded(pgpu_context* ctx, const pgpu_table_layout* in, const void* dev
   return rc;
 }
 
+// The pipeline of a waited query on its own workspace stream, its table being complete: the folded table in ws->fold,
+// the stages' temporary memory in ws->fold_tmp (*temp_bytes of it).  `s` is the caller's: the AVG values move to the
+// device here.
+int fold_on_workspace(pgpu_query* qq, FoldedSpec& s, const FoldedLayout& fl, size_t* temp_bytes) {
+  const pgpu_table_layout& F = fl.layout;
+  int rc = PGPU_OK;
+  Workspace* ws = qq->ws;
+  const size_t tb = *temp_bytes = folded_temp_bytes(qq->layout, s, qq->ctx->num_cus);
+  hipError_t e = ws->fold.ensure(pgpu_table_bytes(&F) + 16, qq->ctx->mpool, ws->stream);
+  if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table fold: %s", hipGetErrorString(e));
+  if (rc == PGPU_OK && s.stage != STAGE_FOLD) {
+    e = ws->fold_tmp.ensure(tb + 16, qq->ctx->mpool, ws->stream);
+    if (e != hipSuccess)
+      rc = fail(PGPU_E_HIP, "table %s: %s", s.runs() ? "runs" : (s.modes() ? "mode" : "select"), hipGetErrorString(e));
+  }
+  if (rc == PGPU_OK && s.avg() && !s.values_on_device) {
+    // the caller's values are read here, into pinned memory the copy to the device may outlive this call from
+    const size_t vb = 8 * (size_t)s.num_values;
+    e = ws->h_mode_vals.ensure(vb);
+    if (e == hipSuccess) e = ws->mode_vals.ensure(vb, qq->ctx->mpool, ws->stream);
+    if (e == hipSuccess) {
+      memcpy(ws->h_mode_vals.p, s.values, vb);
+      e = hipMemcpyAsync(ws->mode_vals.p, ws->h_mode_vals.p, vb, hipMemcpyHostToDevice, ws->stream);
+    }
+    if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table mode: %s", hipGetErrorString(e));
+    s.values = (const double*)ws->mode_vals.p;
+    s.values_on_device = true;
+  }
+  if (rc == PGPU_OK)
+    rc = enqueue_folded(qq->layout, qq->tws->table.p, s, fl, ws->fold.p, ws->fold_tmp.p, tb, qq->ctx->num_cus,
+                        ws->stream);
+  return rc;
+}
+
+// A small folded table (at most 8 MiB) comes back whole into pinned host memory and is compacted there, as
+// pgpu_query_collect does with a small table: one synchronisation.
+int fetch_small_folded(pgpu_query* qq, const pgpu_table_layout& F) {
+  Workspace* ws = qq->ws;
+  const uint64_t fb = pgpu_table_bytes(&F);
+  hipError_t e = ws->h_fold.ensure(fb);
+  if (e == hipSuccess) e = hipMemcpyAsync(ws->h_fold.p, ws->fold.p, fb, hipMemcpyDeviceToHost, ws->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
+  return e == hipSuccess ? PGPU_OK : fail(PGPU_E_HIP, "folded table copy: %s", hipGetErrorString(e));
+}
+
+// The non-empty keys of the fetched table, ascending: their number.  Rows are written while they fit `capacity` (0:
+// none are, and the pointers may be NULL).
+uint64_t small_folded_rows(const pgpu_query* qq, const pgpu_table_layout& F, int64_t* out_keys, int64_t* out_cells,
+                           uint64_t capacity) {
+  const int64_t* t = (const int64_t*)qq->ws->h_fold.p;
+  const int nsec = F.num_sections;
+  uint64_t n = 0;
+  for (uint64_t k = 0; k < F.num_keys; ++k) {
+    if (t[k] <= 0) continue;
+    if (n < capacity) {
+      out_keys[n] = (int64_t)k;
+      for (int sc = 0; sc < nsec; ++sc) out_cells[n * nsec + sc] = t[(size_t)sc * F.num_keys + k];
+    }
+    ++n;
+  }
+  return n;
+}
+
 // pgpu_query_collect_fold, pgpu_query_collect_select, pgpu_query_collect_mode: the wait, the pipeline on the query's
 // workspace, then the resulting table compacted or trimmed.  The query is released on every path.
 int collect_folded(pgpu_query* qq, FoldedSpec s, const pgpu_topk* order, int64_t* out_keys, int64_t* out_cells,
@@ -5402,59 +5495,16 @@ int collect_folded(pgpu_query* qq, FoldedSpec s, const pgpu_topk* order, int64_t
   int rc = pgpu_query_wait(qq, out_stats);
   FoldedLayout fl;
   const pgpu_table_layout& F = fl.layout;
+  size_t tb = 0;
   if (rc == PGPU_OK) rc = folded_layout(qq->layout, s, &fl);
   if (rc == PGPU_OK) rc = check_operands(s);
-  if (rc == PGPU_OK) {
-    // the table is complete (waited above): fold and compact it on the query's own workspace stream
-    Workspace* ws = qq->ws;
-    const size_t tb = folded_temp_bytes(qq->layout, s, qq->ctx->num_cus);
-    hipError_t e = ws->fold.ensure(pgpu_table_bytes(&F) + 16, qq->ctx->mpool, ws->stream);
-    if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table fold: %s", hipGetErrorString(e));
-    if (rc == PGPU_OK && s.stage != STAGE_FOLD) {
-      e = ws->fold_tmp.ensure(tb + 16, qq->ctx->mpool, ws->stream);
-      if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table %s: %s", s.modes() ? "mode" : "select", hipGetErrorString(e));
-    }
-    if (rc == PGPU_OK && s.avg() && !s.values_on_device) {
-      // the caller's values are read here, into pinned memory the copy to the device may outlive this call from
-      const size_t vb = 8 * (size_t)s.num_values;
-      e = ws->h_mode_vals.ensure(vb);
-      if (e == hipSuccess) e = ws->mode_vals.ensure(vb, qq->ctx->mpool, ws->stream);
-      if (e == hipSuccess) {
-        memcpy(ws->h_mode_vals.p, s.values, vb);
-        e = hipMemcpyAsync(ws->mode_vals.p, ws->h_mode_vals.p, vb, hipMemcpyHostToDevice, ws->stream);
-      }
-      if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table mode: %s", hipGetErrorString(e));
-      s.values = (const double*)ws->mode_vals.p;
-      s.values_on_device = true;
-    }
-    if (rc == PGPU_OK)
-      rc = enqueue_folded(qq->layout, qq->tws->table.p, s, fl, ws->fold.p, ws->fold_tmp.p, tb, qq->ctx->num_cus,
-                          ws->stream);
-  }
+  // the table is complete (waited above): fold and compact it on the query's own workspace stream
+  if (rc == PGPU_OK) rc = fold_on_workspace(qq, s, fl, &tb);
   const bool trim = order && order->k > 0 && s.inner_keys > order->k;
   if (rc == PGPU_OK && !trim && pgpu_table_bytes(&F) <= (8u << 20)) {
-    // a small folded table with nothing to trim comes back whole into pinned host memory and is compacted here,
-    // as pgpu_query_collect does with a small table: one synchronisation
-    Workspace* ws = qq->ws;
-    const uint64_t fb = pgpu_table_bytes(&F);
-    hipError_t e = ws->h_fold.ensure(fb);
-    if (e == hipSuccess) e = hipMemcpyAsync(ws->h_fold.p, ws->fold.p, fb, hipMemcpyDeviceToHost, ws->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
-    if (e != hipSuccess) {
-      rc = fail(PGPU_E_HIP, "folded table copy: %s", hipGetErrorString(e));
-    } else {
-      const int64_t* t = (const int64_t*)ws->h_fold.p;
-      const int nsec = F.num_sections;
-      uint64_t n = 0;
-      for (uint64_t k = 0; k < s.inner_keys; ++k) {
-        if (t[k] <= 0) continue;
-        if (n < capacity) {
-          out_keys[n] = (int64_t)k;
-          for (int sc = 0; sc < nsec; ++sc) out_cells[n * nsec + sc] = t[(size_t)sc * s.inner_keys + k];
-        }
-        ++n;
-      }
-      *out_num_groups = n;
+    rc = fetch_small_folded(qq, F);
+    if (rc == PGPU_OK) {
+      const uint64_t n = *out_num_groups = small_folded_rows(qq, F, out_keys, out_cells, capacity);
       if (n > capacity)
         rc = fail(PGPU_E_INVALID, "%llu non-empty groups exceed capacity %llu", (unsigned long long)n,
                   (unsigned long long)capacity);
@@ -5465,6 +5515,129 @@ int collect_folded(pgpu_query* qq, FoldedSpec s, const pgpu_topk* order, int64_t
   }
   if (rc == PGPU_OK && out_layout) *out_layout = F;
   pgpu_query_release(qq);
+  return rc;
+}
+
+// pgpu_table_runs: caller-owned memory, nothing waits for the kernels; the count and the emit back to back.
+int table_runs(pgpu_context* ctx, const pgpu_table_layout* in, const void* dev_table, void* stream, uint64_t inner_keys,
+               void* dev_offsets, void* dev_cids, void* dev_counts, uint64_t run_capacity) {
+  if (!ctx || !in || !dev_table || !dev_offsets || !dev_cids || !dev_counts)
+    return fail(PGPU_E_INVALID, "null argument");
+  FoldedSpec s{STAGE_RUNS, inner_keys};
+  s.run_offsets = (uint64_t*)dev_offsets;
+  FoldedLayout fl;
+  int rc = folded_layout(*in, s, &fl);
+  if (rc) return rc;
+  if (in->num_keys == 0) return fail(PGPU_E_INVALID, "empty table");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  // the temporary memory is taken and given back in stream order
+  const size_t tb = folded_temp_bytes(*in, s, ctx->num_cus);
+  void* temp = nullptr;
+  if (ctx->mpool) HIP_TRY(hipMallocFromPoolAsync(&temp, tb, ctx->mpool, st));
+  else HIP_TRY(hipMallocAsync(&temp, tb, st));
+  rc = enqueue_folded(*in, dev_table, s, fl, nullptr, temp, tb, ctx->num_cus, st);
+  if (rc == PGPU_OK)
+    rc = enqueue_runs_emit(*in, dev_table, s, dev_cids, dev_counts, run_capacity, temp, tb, ctx->num_cus, st);
+  (void)hipFreeAsync(temp, st);
+  return rc;
+}
+
+// pgpu_query_collect_runs: the wait, the fold and the count of the runs on the query's workspace, the number of runs
+// read back, and -- when the caller's buffers hold everything -- the rows compacted and the runs emitted and copied
+// out.  Buffers that are too small keep the query for another call; every other outcome releases it.
+int collect_runs(pgpu_query* qq, uint64_t inner_keys, int64_t* out_keys, int64_t* out_cells, uint64_t capacity,
+                 uint64_t* out_num_groups, uint64_t* out_offsets, uint32_t* out_cids, int64_t* out_counts,
+                 uint64_t run_capacity, uint64_t* out_num_runs, pgpu_query_stats* out_stats,
+                 pgpu_table_layout* out_layout) {
+  if (!qq || !qq->tws) return fail(PGPU_E_INVALID, "query was not submitted");
+  if (!out_num_groups || !out_num_runs) {
+    pgpu_query_release(qq);
+    return fail(PGPU_E_INVALID, "null argument");
+  }
+  // (a cancelled or timed-out query returns here: nothing is folded.  A second call on a kept query waits again,
+  // which returns at once, and folds again: the query's table is only read)
+  int rc = pgpu_query_wait(qq, out_stats);
+  FoldedSpec s{STAGE_RUNS, inner_keys};
+  FoldedLayout fl;
+  const pgpu_table_layout& F = fl.layout;
+  Workspace* ws = qq->ws;
+  size_t tb = 0;
+  uint64_t n = 0, total = 0;
+  bool keep = false;
+  if (rc == PGPU_OK) rc = folded_layout(qq->layout, s, &fl);
+  if (rc == PGPU_OK) {
+    hipError_t e = ws->runs_off.ensure(8 * (inner_keys + 1), qq->ctx->mpool, ws->stream);
+    if (e == hipSuccess) e = ws->h_runs_total.ensure(8);
+    if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table runs: %s", hipGetErrorString(e));
+    s.run_offsets = (uint64_t*)ws->runs_off.p;
+  }
+  if (rc == PGPU_OK) rc = fold_on_workspace(qq, s, fl, &tb);
+  if (rc == PGPU_OK) {
+    // the count first: the collect synchronises anyway, and nothing is emitted that would not fit
+    hipError_t e = hipMemcpyAsync(ws->h_runs_total.p, s.run_offsets + inner_keys, 8, hipMemcpyDeviceToHost, ws->stream);
+    const bool small = pgpu_table_bytes(&F) <= (8u << 20);
+    if (e == hipSuccess && !small) e = hipStreamSynchronize(ws->stream);
+    if (e != hipSuccess) {
+      rc = fail(PGPU_E_HIP, "table runs: %s", hipGetErrorString(e));
+    } else if (small) {
+      // (synchronises: the total is there behind it.  Rows are counted first and written only when they and the runs
+      // fit)
+      rc = fetch_small_folded(qq, F);
+      if (rc == PGPU_OK) {
+        total = *(const uint64_t*)ws->h_runs_total.p;
+        n = small_folded_rows(qq, F, nullptr, nullptr, 0);
+        if (n <= capacity && total <= run_capacity) small_folded_rows(qq, F, out_keys, out_cells, capacity);
+      }
+    } else {
+      // compact_into counts before it writes: no room for rows when the runs do not fit, so that it only counts
+      total = *(const uint64_t*)ws->h_runs_total.p;
+      const uint64_t room = total <= run_capacity ? capacity : 0;
+      rc = compact_into(qq->ctx, ws, &F, ws->fold.p, ws->stream, out_keys, out_cells, room, &n);
+      if (rc == PGPU_E_INVALID && n > room) rc = PGPU_OK;  // its only refusal here: more rows than room (below)
+    }
+    *out_num_groups = n;
+    *out_num_runs = total;
+    if (rc == PGPU_OK && (n > capacity || total > run_capacity)) {
+      keep = true;
+      rc = fail(PGPU_E_INVALID, "%llu groups with %llu value runs exceed the capacities %llu and %llu",
+                (unsigned long long)n, (unsigned long long)total, (unsigned long long)capacity,
+                (unsigned long long)run_capacity);
+    }
+  }
+  if (rc == PGPU_OK) {
+    if (!out_offsets || (total && (!out_cids || !out_counts))) rc = fail(PGPU_E_INVALID, "null argument");
+  }
+  if (rc == PGPU_OK) {
+    // every non-empty key came back, ascending, and an empty key has no run: the runs of row i follow those of row
+    // i - 1, and their number is the row's distinct count, the last section of the folded table
+    const int nsec = F.num_sections;
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+      out_offsets[i] = at;
+      at += (uint64_t)out_cells[i * nsec + (nsec - 1)];
+    }
+    out_offsets[n] = at;
+    if (at != total) rc = fail(PGPU_E_INVALID, "value runs: %llu counted, %llu in the folded table",
+                               (unsigned long long)total, (unsigned long long)at);
+  }
+  if (rc == PGPU_OK && total) {
+    hipError_t e = ws->runs_cids.ensure(4 * total, qq->ctx->mpool, ws->stream);
+    if (e == hipSuccess) e = ws->runs_counts.ensure(8 * total, qq->ctx->mpool, ws->stream);
+    if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table runs: %s", hipGetErrorString(e));
+    if (rc == PGPU_OK)
+      rc = enqueue_runs_emit(qq->layout, qq->tws->table.p, s, ws->runs_cids.p, ws->runs_counts.p, total, ws->fold_tmp.p,
+                             tb, qq->ctx->num_cus, ws->stream);
+    if (rc == PGPU_OK) {
+      e = hipMemcpyAsync(out_cids, ws->runs_cids.p, 4 * total, hipMemcpyDeviceToHost, ws->stream);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(out_counts, ws->runs_counts.p, 8 * total, hipMemcpyDeviceToHost, ws->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
+      if (e != hipSuccess) rc = fail(PGPU_E_HIP, "value runs copy: %s", hipGetErrorString(e));
+    }
+  }
+  if (rc == PGPU_OK && out_layout) *out_layout = F;
+  if (!keep) pgpu_query_release(qq);
   return rc;
 }
 
@@ -5499,6 +5672,18 @@ int pgpu_table_mode(pgpu_context* ctx, const pgpu_table_layout* in_layout, const
                     const double* dev_values, uint64_t num_values, void* dev_out, uint64_t out_bytes) {
   const FoldedSpec s{STAGE_MODE, inner_keys, percentiles, num_percentiles, reducers, dev_values, num_values, true};
   return table_folded(ctx, in_layout, dev_table, stream, s, dev_out, out_bytes);
+}
+
+int pgpu_table_runs(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
+                    uint64_t inner_keys, void* dev_offsets, void* dev_cids, void* dev_counts, uint64_t run_capacity) {
+  return table_runs(ctx, in_layout, dev_table, stream, inner_keys, dev_offsets, dev_cids, dev_counts, run_capacity);
+}
+int pgpu_query_collect_runs(pgpu_query* qq, uint64_t inner_keys, int64_t* out_keys, int64_t* out_cells,
+                            uint64_t capacity, uint64_t* out_num_groups, uint64_t* out_offsets, uint32_t* out_cids,
+                            int64_t* out_counts, uint64_t run_capacity, uint64_t* out_num_runs,
+                            pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
+  return collect_runs(qq, inner_keys, out_keys, out_cells, capacity, out_num_groups, out_offsets, out_cids, out_counts,
+                      run_capacity, out_num_runs, out_stats, out_layout);
 }
 
 int pgpu_query_collect_fold(pgpu_query* qq, uint64_t inner_keys, const pgpu_topk* order, int64_t* out_keys,

@@ -16,6 +16,13 @@ are written by MetadataKey ordinal with INT / LONG values in binary and STRING v
 Java HashMaps are written in their iteration order, which is restated here (String.hashCode, bucket order), so the
 bytes match the reference's byte for byte.
 
+OBJECT cells of the folded functions (ObjectSerDeUtils.java): DISTINCTCOUNT's value set as IntSet / LongSet / FloatSet /
+DoubleSet / StringSet by the column's stored type (:604-766: int size, the elements), PERCENTILE's value list as
+DoubleArrayList (:286-315: int size, the doubles -- the runs expanded), MODE's count map as Int2LongMap .. Double2LongMap
+(:1010-1130: int size, (key, long count) entries).  Elements and entries are written ascending by value, where the
+reference writes its hash table's iteration order: its deserialisers re-insert every element, so they do not depend on
+the order, but the bytes of such a cell are the reference's only up to that permutation.
+
 Broker side: ``GroupByDataTableReducer`` / ``AggregationDataTableReducer`` (core/query/reduce/GroupByDataTableReducer
 .java:85-223) merge the servers' intermediate results per group (AggregationFunction.merge), extract the final
 results, apply ORDER BY and LIMIT, and sum the servers' statistics.
@@ -27,7 +34,10 @@ import struct
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
-from .query import QueryContext
+from ._lib import PGPU_DOUBLE, PGPU_E_UNSUPPORTED, PGPU_FLOAT, PGPU_INT, PGPU_LONG, PGPU_STRING, UnsupportedPlanError
+from .distinct import (FOLDED, ValueList, ValueMap, ValueSet, merge_runs, runs_mode, runs_percentile, value_key,
+                       value_order)
+from .query import QueryContext, java_double_string
 
 VERSION_3 = 3
 HEADER_SIZE = 4 * 13
@@ -47,6 +57,70 @@ METADATA_KEYS = [("unknown", "S"), ("table", "S"), ("numDocsScanned", "L"), ("nu
 _KEY_ORDINAL = {name: i for i, (name, _) in enumerate(METADATA_KEYS)}
 
 OBJECT_TYPE_AVG_PAIR = 4  # ObjectSerDeUtils.ObjectType.AvgPair
+OBJECT_TYPE_DOUBLE_ARRAY_LIST = 3
+# stored type -> (ObjectType value, struct format of an element / key); a set's elements, a map's keys
+_SET_TYPES = {PGPU_INT: (9, "i"), PGPU_LONG: (15, "q"), PGPU_FLOAT: (16, "f"), PGPU_DOUBLE: (17, "d"),
+              PGPU_STRING: (18, None)}
+_MAP_TYPES = {PGPU_INT: (23, "i"), PGPU_LONG: (24, "q"), PGPU_FLOAT: (25, "f"), PGPU_DOUBLE: (26, "d")}
+MAX_CELL_BYTES = (1 << 31) - 1  # a Java byte[]
+
+
+def object_bytes(v) -> bytes:
+    """int ObjectType value + ObjectSerDeUtils bytes of an OBJECT cell: an AvgPair (sum, count), a ValueSet, a ValueList
+    or a ValueMap.  A cell past 2^31 - 1 bytes is refused before it is built."""
+    def sized(n: int) -> None:
+        if 4 + n > MAX_CELL_BYTES:
+            raise UnsupportedPlanError(PGPU_E_UNSUPPORTED, f"an OBJECT cell of {4 + n} bytes (a Java array holds "
+                                                           f"{MAX_CELL_BYTES})")
+    if isinstance(v, ValueSet):
+        otype, fmt = _SET_TYPES[v.stored_type]
+        if fmt is None:  # Set<String>: int length + UTF-8 bytes per element
+            enc = [x.encode("utf-8") for x in v.values]
+            sized(4 + sum(4 + len(b) for b in enc))
+            body = b"".join(struct.pack(">i", len(b)) + b for b in enc)
+        else:
+            sized(4 + struct.calcsize(fmt) * len(v.values))
+            body = struct.pack(f">{len(v.values)}{fmt}", *v.values)
+        return struct.pack(">ii", otype, len(v.values)) + body
+    if isinstance(v, ValueList):
+        n = int(sum(v.counts))
+        sized(4 + 8 * n)
+        body = b"".join(struct.pack(">d", float(x)) * int(c) for x, c in zip(v.values, v.counts))
+        return struct.pack(">ii", OBJECT_TYPE_DOUBLE_ARRAY_LIST, n) + body
+    if isinstance(v, ValueMap):
+        otype, fmt = _MAP_TYPES[v.stored_type]
+        sized(4 + (struct.calcsize(fmt) + 8) * len(v.values))
+        body = b"".join(struct.pack(f">{fmt}q", x, int(c)) for x, c in zip(v.values, v.counts))
+        return struct.pack(">ii", otype, len(v.values)) + body
+    return struct.pack(">idq", OBJECT_TYPE_AVG_PAIR, float(v[0]), int(v[1]))
+
+
+def object_from_bytes(var: bytes, off: int):
+    """The OBJECT cell at `off` of the variable-size section (object_bytes' inverse)."""
+    (otype,) = struct.unpack_from(">i", var, off)
+    if otype == OBJECT_TYPE_AVG_PAIR:
+        return struct.unpack_from(">dq", var, off + 4)
+    (n,) = struct.unpack_from(">i", var, off + 4)
+    pos = off + 8
+    for stored, (t, fmt) in _SET_TYPES.items():
+        if t != otype:
+            continue
+        if fmt is not None:
+            return ValueSet(list(struct.unpack_from(f">{n}{fmt}", var, pos)), stored)
+        vals = []
+        for _ in range(n):
+            (ln,) = struct.unpack_from(">i", var, pos)
+            vals.append(var[pos + 4: pos + 4 + ln].decode("utf-8"))
+            pos += 4 + ln
+        return ValueSet(vals, stored)
+    if otype == OBJECT_TYPE_DOUBLE_ARRAY_LIST:  # any order on the wire: the runs are rebuilt
+        values, counts = merge_runs([(struct.unpack_from(f">{n}d", var, pos), [1] * n)])
+        return ValueList(values, counts)
+    for stored, (t, fmt) in _MAP_TYPES.items():
+        if t == otype:
+            flat = struct.unpack_from(">" + f"{fmt}q" * n, var, pos)
+            return ValueMap(list(flat[0::2]), list(flat[1::2]), stored)
+    raise ValueError(f"object type {otype}")
 
 
 # ---- Java HashMap iteration order -----------------------------------------------------------------------------------
@@ -104,7 +178,8 @@ class DataSchema:
 
 @dataclass
 class DataTable:
-    """A DataTable's content: schema, rows of Python values (OBJECT AvgPair cells as (sum, count)), metadata
+    """A DataTable's content: schema, rows of Python values (OBJECT cells: an AvgPair as (sum, count), the folded
+    functions' as distinct.ValueSet / ValueList / ValueMap), metadata
     (MetadataKey name -> string value, inserted in the order the server puts them) and exceptions."""
 
     schema: Optional[DataSchema]
@@ -135,10 +210,10 @@ class DataTable:
                             d = dictionaries[name] = {}
                             dict_order.append(name)
                         fixed += struct.pack(">i", d.setdefault(v, len(d)))
-                    elif t == OBJECT:  # AvgPair: (offset, length) | type, double sum, long count
-                        payload = struct.pack(">dq", float(v[0]), int(v[1]))
-                        fixed += struct.pack(">ii", len(var), len(payload))
-                        var += struct.pack(">i", OBJECT_TYPE_AVG_PAIR) + payload
+                    elif t == OBJECT:  # (offset, length of the object's own bytes) | type, the object's bytes
+                        cell = object_bytes(v)
+                        fixed += struct.pack(">ii", len(var), len(cell) - 4)
+                        var += cell
                     else:
                         raise ValueError(f"column type {t} is not produced on this path")
         exc = bytearray(struct.pack(">i", len(self.exceptions)))
@@ -234,10 +309,7 @@ class DataTable:
                         row.append(dicts[name][struct.unpack_from(">i", fixed, pos)[0]])
                     elif t == OBJECT:
                         off, ln = struct.unpack_from(">ii", fixed, pos)
-                        (otype,) = struct.unpack_from(">i", var, off)
-                        if otype != OBJECT_TYPE_AVG_PAIR:
-                            raise ValueError(f"object type {otype}")
-                        row.append(struct.unpack_from(">dq", var, off + 4))
+                        row.append(object_from_bytes(var, off))
                     else:
                         raise ValueError(f"column type {t}")
                     pos += w
@@ -278,8 +350,17 @@ def _agg_column(a, result_name: bool) -> Tuple[str, str]:
     """(column name, intermediate result type) of an aggregation: getResultColumnName ("sum(m)", "count(*)") in a
     group-by schema, getColumnName ("sum_m", "count_star") in an aggregation-only one
     (BaseSingleInputAggregationFunction.java:42-49, CountAggregationFunction.java:36-56); LONG for COUNT / COUNTMV,
-    OBJECT (AvgPair) for AVG / AVGMV, DOUBLE otherwise (getIntermediateResultColumnType)."""
+    OBJECT (AvgPair) for AVG / AVGMV, OBJECT (the value set, list or count map) for DISTINCTCOUNT / PERCENTILE / MODE
+    -- distinctCount_c, percentile95_c or percentile95.5_c (PercentileAggregationFunction.java:59-70), mode_c --,
+    DOUBLE otherwise (getIntermediateResultColumnType)."""
     fn = a.function
+    if fn in FOLDED:
+        if result_name:
+            return a.result_name, OBJECT
+        if fn == "PERCENTILE":
+            p = java_double_string(a.percentile) if a.percentile_arg else str(int(a.percentile))
+            return f"percentile{p}_{a.column}", OBJECT
+        return f"{'distinctCount' if fn == 'DISTINCTCOUNT' else 'mode'}_{a.column}", OBJECT
     t = _TYPE_NAME[fn]
     if fn == "COUNT":
         name = "count(*)" if result_name else "count_star"
@@ -288,13 +369,13 @@ def _agg_column(a, result_name: bool) -> Tuple[str, str]:
     return name, {"COUNT": LONG, "COUNTMV": LONG, "AVG": OBJECT, "AVGMV": OBJECT}.get(fn, DOUBLE)
 
 
-def _refuse_distinct(query: QueryContext) -> None:
+def _refuse_distinct(query: QueryContext, carries_value_sets: bool = False) -> None:
     """DISTINCTCOUNT's broker-mergeable intermediate is the value set (DistinctCountAggregationFunction.java:252-310),
     PERCENTILE's the value list (PercentileAggregationFunction.java:82-100) and MODE's the value -> count map
-    (ModeAggregationFunction.java:416-456), which the folded table no longer holds: no DataTable for such a query."""
+    (ModeAggregationFunction.java:416-456), which the folded table no longer holds: no DataTable for such a query
+    unless its result collected them (GpuPlanMaker.execute_mergeable)."""
     from .distinct import folded_names, has_distinct
-    if has_distinct(query):
-        from ._lib import PGPU_E_UNSUPPORTED, UnsupportedPlanError
+    if has_distinct(query) and not carries_value_sets:
         raise UnsupportedPlanError(PGPU_E_UNSUPPORTED, f"no DataTable for a {folded_names(query)} query: its "
                                                        "intermediate result is the value set, list or count map")
 
@@ -304,7 +385,7 @@ def server_data_table(query: QueryContext, result, group_types: Sequence[int] = 
     IndexedTable returns (group values + intermediate results) or the one aggregation row, with the statistics
     attachMetadataToDataTable puts (numResizes / resizeTimeMs 0: the GPU table never resizes).  `group_types`: the
     group columns' stored types (PGPU_INT ...)."""
-    _refuse_distinct(query)
+    _refuse_distinct(query, bool(getattr(result, "value_sets", False)))
     aggs = [_agg_column(a, bool(query.group_by)) for a in query.aggregations]
     if query.group_by:
         schema = DataSchema(list(query.group_by) + [n for n, _ in aggs],
@@ -334,7 +415,16 @@ def _group_key(v):
 
 
 def _merge(fn: str, a, b):
-    """AggregationFunction.merge of two intermediate results."""
+    """AggregationFunction.merge of two intermediate results.  DISTINCTCOUNT: the union of the sets with fastutil's key
+    equality (floatToIntBits / doubleToLongBits: one NaN, -0.0 apart from 0.0); PERCENTILE: the lists concatenated
+    (their runs united); MODE: the maps merged by Long::sum (ModeAggregationFunction.java:425-455)."""
+    if fn == "DISTINCTCOUNT":
+        uniq = {value_key(v): v for v in list(a.values) + list(b.values)}
+        return ValueSet(sorted(uniq.values(), key=value_order), a.stored_type)
+    if fn == "PERCENTILE":
+        return ValueList(*merge_runs([(a.values, a.counts), (b.values, b.counts)]))
+    if fn == "MODE":
+        return ValueMap(*merge_runs([(a.values, a.counts), (b.values, b.counts)]), a.stored_type)
     if fn in ("COUNT", "SUM", "COUNTMV", "SUMMV"):
         return a + b
     if fn in ("MIN", "MINMV"):
@@ -344,8 +434,16 @@ def _merge(fn: str, a, b):
     return (a[0] + b[0], a[1] + b[1])  # AVG / AVGMV: AvgPair
 
 
-def _final(fn: str, v):
-    """AggregationFunction.extractFinalResult."""
+def _final(fn: str, v, agg=None):
+    """AggregationFunction.extractFinalResult (agg: the aggregation itself, for a percentile or a mode's reducer).
+    DISTINCTCOUNT: the set's size as an INT; PERCENTILE: the sorted list at pgpu_select.hip's select_rank, -inf when
+    empty; MODE: the reducers of ModeAggregationFunction.java:486-672, -inf when empty."""
+    if fn == "DISTINCTCOUNT":
+        return len(v.values)
+    if fn == "PERCENTILE":
+        return runs_percentile(*merge_runs([(v.values, v.counts)]), agg.percentile)
+    if fn == "MODE":
+        return runs_mode(*merge_runs([(v.values, v.counts)]), agg.reducer)
     if fn in ("AVG", "AVGMV"):
         return -math.inf if v[1] == 0 else v[0] / v[1]
     if fn in ("COUNT", "COUNTMV"):
@@ -369,7 +467,10 @@ class BrokerResult:
 def reduce_data_tables(query: QueryContext, tables: Sequence[DataTable]) -> BrokerResult:
     """GroupByDataTableReducer / AggregationDataTableReducer over the servers' DataTables."""
     from .plan import order_and_limit, to_select_order
-    _refuse_distinct(query)
+    folded = [i for i, a in enumerate(query.aggregations) if a.function in FOLDED]
+    ngc = len(query.group_by)
+    _refuse_distinct(query, all(t.schema is None or all(t.schema.column_types[ngc + i] == OBJECT for i in folded)
+                                for t in tables))
     res = BrokerResult(rows=[])
     for t in tables:
         md = t.metadata
@@ -381,7 +482,8 @@ def reduce_data_tables(query: QueryContext, tables: Sequence[DataTable]) -> Brok
         res.total_docs += int(md.get("totalDocs", 0))
         res.num_groups_limit_reached |= md.get("numGroupsLimitReached") == "true"
         res.exceptions.update(t.exceptions)
-    fns = [a.function for a in query.aggregations]
+    aggs = list(query.aggregations)
+    fns = [a.function for a in aggs]
     ng = len(query.group_by)
     merged: Dict[tuple, list] = {}
     values: Dict[tuple, tuple] = {}
@@ -401,9 +503,10 @@ def reduce_data_tables(query: QueryContext, tables: Sequence[DataTable]) -> Brok
         inter = merged.get((), None)
         if inter is None:  # no server had a row: the functions' empty results
             inter = [{"COUNT": 0, "COUNTMV": 0, "MIN": math.inf, "MINMV": math.inf, "MAX": -math.inf,
-                      "MAXMV": -math.inf, "AVG": (0.0, 0), "AVGMV": (0.0, 0)}.get(fn, 0.0) for fn in fns]
-        res.rows = [to_select_order(query, tuple(_final(fn, v) for fn, v in zip(fns, inter)))]
+                      "MAXMV": -math.inf, "AVG": (0.0, 0), "AVGMV": (0.0, 0), "DISTINCTCOUNT": ValueSet([], PGPU_INT),
+                      "PERCENTILE": ValueList([], []), "MODE": ValueMap([], [], PGPU_INT)}.get(fn, 0.0) for fn in fns]
+        res.rows = [to_select_order(query, tuple(_final(fn, v, a) for fn, v, a in zip(fns, inter, aggs)))]
         return res
-    finals = [values[k] + tuple(_final(fn, v) for fn, v in zip(fns, merged[k])) for k in merged]
+    finals = [values[k] + tuple(_final(fn, v, a) for fn, v, a in zip(fns, merged[k], aggs)) for k in merged]
     res.rows = [to_select_order(query, r) for r in order_and_limit(query, finals)]
     return res

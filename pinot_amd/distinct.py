@@ -26,6 +26,12 @@ of several such values the smallest, the largest or their mean, :59-75) rides th
 ``cid`` are that map, and one reduction behind the fold (pgpu_query_collect_mode) leaves per group the largest count,
 the number of tied ids, the smallest and the largest of them and -- for the AVG reducer -- the sum of their values.  The
 pass of ``c`` carries every MODE of ``c`` whatever its reducer: one table, one fold, one mode reduction.
+
+Those are final values, right for a table on one server.  What a broker merges across servers is the value set, the
+value list and the value -> count map, and the counts of ``Q'`` along ``cid`` are all three: the mergeable execution
+(GpuPlanMaker.execute_mergeable) runs the same passes and collects, per group, the occupied ``cid`` with their counts --
+value runs (pgpu_query_collect_runs) -- from which ``raise_runs`` computes the same rows on the host and the
+intermediates ``ValueSet`` / ``ValueList`` / ``ValueMap`` (written and merged by pinot_amd/datatable.py).
 """
 from __future__ import annotations
 
@@ -230,6 +236,163 @@ def value_keys(values) -> set:
     """value_key of every entry of a dictionary (numpy array or list of strings) or list of group values."""
     vals = values.tolist() if hasattr(values, "tolist") else list(values)
     return {value_key(v) for v in vals}
+
+
+# ---- the mergeable intermediates: value runs (pgpu_query_collect_runs) ----------------------------------------------
+@dataclass
+class ValueSet:
+    """DISTINCTCOUNT's intermediate (DistinctCountAggregationFunction.java:252-310): the distinct values, ascending."""
+    values: list
+    stored_type: int  # PGPU_INT .. PGPU_STRING: which of the reference's sets it is on the wire
+
+
+@dataclass
+class ValueList:
+    """PERCENTILE's intermediate (PercentileAggregationFunction.java:82-100), a list of doubles, kept as runs: the
+    ascending distinct values with their counts."""
+    values: list
+    counts: list
+
+
+@dataclass
+class ValueMap:
+    """MODE's intermediate (ModeAggregationFunction.java:416-456), value -> count, ascending by value."""
+    values: list
+    counts: list
+    stored_type: int  # PGPU_INT .. PGPU_DOUBLE: which of the reference's maps it is on the wire
+
+
+def value_order(v):
+    """Sort key of column values as Arrays.sort orders doubles: -0.0 before 0.0, NaN last."""
+    if isinstance(v, float):
+        return (1, 0.0, 0.0) if math.isnan(v) else (0, v, math.copysign(1.0, v))
+    return v
+
+
+def merge_runs(parts) -> Tuple[list, list]:
+    """(values, counts) of several runs united: counts of one value (value_key: by bits, one NaN) added, ascending."""
+    acc: Dict[object, list] = {}
+    for values, counts in parts:
+        for v, c in zip(values, counts):
+            e = acc.get(value_key(v))
+            if e is None:
+                acc[value_key(v)] = [v, int(c)]
+            else:
+                e[1] += int(c)
+    items = sorted(acc.values(), key=lambda e: value_order(e[0]))
+    return [e[0] for e in items], [e[1] for e in items]
+
+
+def select_rank(n: int, p: float) -> int:
+    """pgpu_select.hip's select_rank: PercentileAggregationFunction.java:152-165 in IEEE double."""
+    if p == 100.0:
+        return n - 1
+    return min(int(float(n) * p / 100.0), n - 1)
+
+
+def runs_percentile(values, counts, p: float) -> float:
+    """The percentile of sorted runs; no value: DEFAULT_FINAL_RESULT."""
+    n = int(sum(counts))
+    if n <= 0:
+        return -math.inf
+    r, run = select_rank(n, p), 0
+    for v, c in zip(values, counts):
+        run += c
+        if run > r:
+            return float(v)
+    return float(values[-1])
+
+
+def runs_mode(values, counts, reducer: str) -> float:
+    """ModeAggregationFunction.java:486-672 over ascending runs: the value of the largest count, of several the
+    smallest, the largest or their mean (each converted to double before it is added); none: DEFAULT_FINAL_RESULT."""
+    if not len(values):
+        return -math.inf
+    m = max(counts)
+    tied = [v for v, c in zip(values, counts) if c == m]
+    if reducer == "MIN":
+        return float(tied[0])
+    if reducer == "MAX":
+        return float(tied[-1])
+    s = 0.0
+    for v in tied:
+        s += float(v)
+    return s / len(tied)
+
+
+@dataclass
+class PassRuns:
+    """What one pass's pgpu_query_collect_runs brought back: the folded rows decoded (a QueryResult of the pass's
+    plain aggregations + DISTINCTCOUNT(column), groups ascending by key) and the runs of those rows."""
+    result: object          # QueryResult
+    offsets: object         # uint64 [rows + 1]
+    cids: object            # uint32 [runs]: ids of `dictionary`
+    counts: object          # int64 [runs]
+    dictionary: object      # the global dictionary of the pass's column (numpy array or list of str)
+    stored_type: int
+
+
+def raise_runs(query: QueryContext, passes: Sequence[DistinctPass], runs: Sequence[PassRuns]):
+    """The original query's QueryResult from the passes' value runs: finals computed here on the host, and the
+    intermediates -- ValueSet per DISTINCTCOUNT, ValueList per PERCENTILE, ValueMap per MODE -- per group."""
+    from .plan import QueryResult, order_and_limit, to_select_order
+
+    res = QueryResult(query=query, stats=_join_stats(query, [pr.result for pr in runs]))
+    res.value_sets = True
+    na = len(query.aggregations)
+    ng = len(query.group_by)
+
+    def place(fin: list, inter: list, p: DistinctPass, pr: PassRuns, row: int, vals: Sequence, ivals: Sequence) -> None:
+        for j, i in enumerate(p.plain):
+            fin[i], inter[i] = vals[j], ivals[j]
+        lo, hi = (int(pr.offsets[row]), int(pr.offsets[row + 1])) if row >= 0 else (0, 0)
+        d = pr.dictionary
+        ids = pr.cids[lo:hi]
+        values = [d[int(c)] for c in ids] if isinstance(d, list) else d[ids].tolist()
+        counts = pr.counts[lo:hi].tolist()
+        for i in p.distinct:
+            fin[i], inter[i] = len(values), ValueSet(values, pr.stored_type)
+        if p.percentile:
+            fv = [float(v) for v in values]
+            for i in p.percentile:
+                fin[i] = runs_percentile(values, counts, query.aggregations[i].percentile)
+                inter[i] = ValueList(fv, counts)
+        for i in p.mode:
+            fin[i] = runs_mode(values, counts, query.aggregations[i].reducer)
+            inter[i] = ValueMap(values, counts, pr.stored_type)
+
+    def pass_intermediate(r) -> dict:
+        if r._intermediate is None and r._columns is not None:
+            r._intermediate = r._columns.intermediate()
+        return r._intermediate or {}
+
+    if not ng:
+        fin, inter = [None] * na, [None] * na
+        for p, pr in zip(passes, runs):
+            nrows = len(pr.offsets) - 1
+            place(fin, inter, p, pr, 0 if nrows else -1, pr.result.aggregation_result, pass_intermediate(pr.result)[()])
+        res.aggregation_result = fin
+        res._intermediate = {(): inter}
+        res.rows = [to_select_order(query, tuple(fin))]
+        return res
+    # every pass returns every group the filter meets, ascending by key: the row of a group is the same in all
+    index = [{tuple(r[:ng]): k for k, r in enumerate(pr.result.group_rows)} for pr in runs]
+    inters = [pass_intermediate(pr.result) for pr in runs]
+    rows, merged = [], {}
+    for k, r in enumerate(runs[0].result.group_rows):
+        key = tuple(r[:ng])
+        if not all(key in m for m in index[1:]):
+            continue
+        fin, inter = [None] * na, [None] * na
+        for p, pr, m, im in zip(passes, runs, index, inters):
+            row = m[key]
+            place(fin, inter, p, pr, row, pr.result.group_rows[row][ng:], im[key])
+        rows.append(key + tuple(fin))
+        merged[key] = inter
+    res._group_rows = rows
+    res._intermediate = merged
+    res.rows = [to_select_order(query, r) for r in order_and_limit(query, rows)]
+    return res
 
 
 def unfolded_result(query: QueryContext, passes: Sequence[DistinctPass], results: Sequence):

@@ -333,6 +333,7 @@ class QueryResult:
         self._group_rows: Optional[List[tuple]] = None
         self._intermediate: Optional[dict] = None
         self.value_dictionary = None  # a folded pass: the global dictionary of the folded column
+        self.value_sets = False  # execute_mergeable: the intermediates of the folded functions were collected
 
     @property
     def group_rows(self) -> Optional[List[tuple]]:
@@ -343,10 +344,11 @@ class QueryResult:
 
     @property
     def intermediate(self) -> Optional[dict]:
-        """group values -> intermediate values (AVG as (sum, count))."""
-        if has_distinct(self.query):
+        """group values -> intermediate values (AVG as (sum, count); from GpuPlanMaker.execute_mergeable DISTINCTCOUNT
+        as a distinct.ValueSet, PERCENTILE as a ValueList, MODE as a ValueMap)."""
+        if has_distinct(self.query) and not self.value_sets:
             # the broker-mergeable form of DISTINCTCOUNT is the value set and that of PERCENTILE the value list, which
-            # the folded table no longer holds
+            # the folded table no longer holds: execute_mergeable collects them
             raise UnsupportedPlanError(_lib.PGPU_E_UNSUPPORTED,
                                        f"no intermediate result for a {folded_names(self.query)} query")
         if self._intermediate is None and self._columns is not None:
@@ -556,6 +558,9 @@ class GpuPlanMaker:
         # changes.
         self._prepared: Dict[tuple, tuple] = {}
         self._distinct: Dict[int, tuple] = {}  # id(query) -> (query, its DISTINCTCOUNT passes)
+        # execute_mergeable: the value runs a pass's first pgpu_query_collect_runs has room for (it is repeated once
+        # with the count the library asks for)
+        self.run_capacity = 1 << 22
         if hasattr(ctx, "add_listener"):
             ctx.add_listener(self)  # segment_released: forget global dictionaries naming a released segment
 
@@ -1032,21 +1037,133 @@ class GpuPlanMaker:
                                                              C.byref(n), C.byref(st)))
         table = GroupTable.sorted(keys[: n.value * kw].reshape(-1, kw) if kw > 1 else keys[: n.value],
                                   cells[: n.value], L)
-        stats = ExecutionStats(num_docs_scanned=st.num_docs_scanned,
-                               num_entries_scanned_in_filter=st.num_entries_scanned_in_filter,
-                               num_entries_scanned_post_filter=st.num_docs_scanned * len(query.projected_columns),
-                               num_total_docs=st.num_total_docs, num_segments_processed=pending.num_segments,
-                               kernel_ms=st.kernel_ms, sparse_sector_bytes=st.sparse_sector_bytes,
-                               dense_bytes=st.dense_bytes, filter_stats_exact=bool(st.filter_stats_exact),
-                               num_groups_limit_reached=bool(st.num_groups_limit_reached),
-                               num_segments_matched=st.num_segments_matched,
-                               segment_matched=pending.matched[:pending.num_segments].copy(),
-                               kernel_variant=st.kernel_variant)
+        stats = self._stats_of(st, query, pending)
         gdicts = [g[0] for g in pending.globals_]
         if fold is None:
             return finish(query, table, gdicts, stats)
         res = finish(query, table, gdicts[:-1], stats)
         res.value_dictionary = gdicts[-1]
+        return res
+
+    @staticmethod
+    def _stats_of(st: QueryStats, query: QueryContext, pending: "PendingQuery") -> ExecutionStats:
+        """The statistics of a collected launch."""
+        return ExecutionStats(num_docs_scanned=st.num_docs_scanned,
+                              num_entries_scanned_in_filter=st.num_entries_scanned_in_filter,
+                              num_entries_scanned_post_filter=st.num_docs_scanned * len(query.projected_columns),
+                              num_total_docs=st.num_total_docs, num_segments_processed=pending.num_segments,
+                              kernel_ms=st.kernel_ms, sparse_sector_bytes=st.sparse_sector_bytes,
+                              dense_bytes=st.dense_bytes, filter_stats_exact=bool(st.filter_stats_exact),
+                              num_groups_limit_reached=bool(st.num_groups_limit_reached),
+                              num_segments_matched=st.num_segments_matched,
+                              segment_matched=pending.matched[:pending.num_segments].copy(),
+                              kernel_variant=st.kernel_variant)
+
+    # -- the mergeable execution of DISTINCTCOUNT / PERCENTILE / MODE: value runs (pinot_amd/distinct.py) --
+    def submit_mergeable(self, query: QueryContext, segments: Sequence[GpuSegment]):
+        """submit() for a result a broker can merge with other servers': the same lowering and passes as submit()
+        gives a DISTINCTCOUNT / PERCENTILE / MODE query, all in flight, collected through pgpu_query_collect_runs --
+        without the server's ORDER BY trim, which is not applied to value-set results (the broker's reduce over a
+        superset of the trimmed rows gives the same answer)."""
+        if not has_distinct(query):
+            return self.submit(query, segments)
+        pending = self.submit_distinct(query, segments)
+        for p, pq in zip(pending.passes, pending.pending):
+            pq.order = None
+            # the column's stored type names its wire type (IntSet or LongSet ...): one schema over a table's segments
+            pq.stored_type = segments[0].column(p.column).data_type if segments else PGPU_INT
+        pending.mergeable = True
+        return pending
+
+    def collect_mergeable(self, pending) -> QueryResult:
+        """collect() of submit_mergeable: the passes' value runs, decoded through their global dictionaries and raised
+        to the original query's result with its intermediates (distinct.raise_runs)."""
+        if not (isinstance(pending, DistinctPending) and pending.mergeable):
+            return self.collect(pending)
+        from .distinct import raise_runs
+        runs, err = [], None
+        for pq in pending.pending:
+            try:
+                runs.append(self._collect_runs(pq))
+            except _lib.PinotGpuError as e:
+                err = err or e
+        pending.pending = []
+        if err is not None:
+            raise err
+        return raise_runs(pending.query, pending.passes, runs)
+
+    def _collect_runs(self, pending: "PendingQuery"):
+        """One pass of submit_mergeable through pgpu_query_collect_runs: its folded rows (the plain aggregations and the distinct count)
+        and the runs of its column per row.  The run capacity starts at min(run_capacity = 2^22, the key space of
+        Q') and the call is repeated once with the count it asked for."""
+        from .distinct import DISTINCT, PassRuns
+        lib = self.ctx._lib
+        fold = pending.fold
+        F = _lib.folded_layout_of(pending.layout, fold.inner_keys, 0, 0)
+        nsec = F.num_sections
+        cap = int(min(F.num_keys, 1 << 26))
+        rcap = int(min(self.run_capacity, pending.layout.num_keys))
+        n, nr, st = C.c_uint64(), C.c_uint64(), QueryStats()
+        h, pending.handle = pending.handle, None
+        for attempt in (0, 1):
+            keys = np.empty(max(cap, 1), dtype=np.int64)
+            cells = np.empty((max(cap, 1), nsec), dtype=np.int64)
+            offsets = np.empty(cap + 1, dtype=np.uint64)
+            cids = np.empty(max(rcap, 1), dtype=np.uint32)
+            counts = np.empty(max(rcap, 1), dtype=np.int64)
+            rc = lib.pgpu_query_collect_runs(h, fold.inner_keys, keys.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             cells.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(n),
+                                             offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                             cids.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                             counts.ctypes.data_as(C.POINTER(C.c_int64)), rcap, C.byref(nr),
+                                             C.byref(st), None)
+            kept = rc == _lib.PGPU_E_INVALID and (n.value > cap or nr.value > rcap)  # too small: the query is kept
+            if not kept:
+                break
+            if attempt:
+                lib.pgpu_query_release(h)
+                break
+            cap, rcap = max(cap, n.value), max(rcap, nr.value)
+        _lib.check(rc)
+        q = fold.query
+        aggs = [a for a in q.aggregations if a.function not in FOLDED] + [AggregationSpec(DISTINCT, pending.query.group_by[-1])]
+        q = dataclasses.replace(q, select=list(q.group_by) + aggs, aggregations=aggs)
+        table = GroupTable(keys[: n.value], cells[: n.value], F)
+        gdicts = [g[0] for g in pending.globals_]
+        res = finish(q, table, gdicts[:-1], self._stats_of(st, q, pending))
+        return PassRuns(res, offsets[: n.value + 1], cids[: nr.value], counts[: nr.value], gdicts[-1],
+                        pending.stored_type)
+
+    def execute_mergeable(self, query: QueryContext, segments: Sequence[GpuSegment]) -> QueryResult:
+        """execute() with a result whose ``intermediate`` a broker can merge (datatable.server_data_table): for a query
+        with DISTINCTCOUNT / PERCENTILE / MODE the value sets, lists and count maps per group, collected as value runs
+        from the device; rows, group_rows, aggregation_result and statistics as execute() gives them, computed here on
+        the host from the runs.  Any other query is execute()."""
+        if not has_distinct(query):
+            return self.execute(query, segments)
+        non_scan = self.non_scan_segments(query, segments)
+        if not any(non_scan):
+            return self.collect_mergeable(self.submit_mergeable(query, segments))
+        # as execute_distinct: a non-scan segment contributes its dictionary to the set
+        from .distinct import ValueSet, value_key, value_keys, value_order
+        rest = [s for s, ns in zip(segments, non_scan) if not ns]
+        meta = [s for s, ns in zip(segments, non_scan) if ns]
+        scanned = self.collect_mergeable(self.submit_mergeable(query, rest)) if rest else None
+        sets, found = {}, {}
+        for ai, a in enumerate(query.aggregations):
+            if a.function != "DISTINCTCOUNT":
+                continue
+            vals = list(scanned.intermediate[()][ai].values) if scanned is not None else []
+            for s in meta:
+                d = s.dictionaries[a.column]
+                vals += d.tolist() if hasattr(d, "tolist") else list(d)
+            uniq = {value_key(v): v for v in vals}
+            found[ai] = ValueSet(sorted(uniq.values(), key=value_order), meta[0].column(a.column).data_type)
+            sets[ai] = value_keys(scanned.intermediate[()][ai].values) if scanned is not None else set()
+        res = merge_non_scan(query, scanned, meta, sets)
+        for ai, vs in found.items():
+            res._intermediate[()][ai] = vs
+        res.value_sets = True
         return res
 
     def execute(self, query: QueryContext, segments: Sequence[GpuSegment]) -> QueryResult:
@@ -1177,6 +1294,7 @@ class PendingQuery:
     matched: Optional[np.ndarray] = None  # per-segment matched flags, filled by the wait (pgpu_query_matched_segments)
     order: Optional[object] = None  # the pgpu_topk given at submit (collect passes the same one)
     fold: Optional["FoldedPass"] = None  # a DISTINCTCOUNT / PERCENTILE / MODE pass: collected through the fold
+    stored_type: int = PGPU_INT  # submit_mergeable: the stored type of the pass's column (PGPU_INT ..)
 
     def cancel(self) -> None:
         """Stop the query (pgpu_query_cancel): its kernels skip their remaining tiles and collect raises
@@ -1527,6 +1645,7 @@ class DistinctPending:
     query: QueryContext
     passes: list
     pending: List[PendingQuery]
+    mergeable: bool = False  # submit_mergeable: collected as value runs
 
     def cancel(self) -> None:
         for pq in self.pending:
