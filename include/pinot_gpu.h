@@ -274,7 +274,9 @@ typedef struct {
 /* (fn values above PGPU_AGG_AVG are PGPU_E_UNSUPPORTED.  DISTINCTCOUNT and PERCENTILE are no descriptor functions:
  * each is a GROUP BY on the column, folded at collect -- pgpu_query_collect_fold below -- and, for PERCENTILE, with the
  * rank selected along the column's ids behind the fold -- pgpu_query_collect_select.  MODE likewise, with the largest
- * count along the column's ids found behind the fold -- pgpu_query_collect_mode.) */
+ * count along the column's ids found behind the fold -- pgpu_query_collect_mode.  DISTINCTCOUNTHLL and
+ * DISTINCTCOUNTRAWHLL likewise, with the HyperLogLog registers of the occupied ids raised beside the fold --
+ * pgpu_query_collect_hll.) */
 
 typedef struct {
   int32_t fn;
@@ -695,6 +697,52 @@ int pgpu_query_collect_runs(pgpu_query* query, uint64_t inner_keys, int64_t* out
                             uint64_t capacity, uint64_t* out_num_groups, uint64_t* out_offsets, uint32_t* out_cids,
                             int64_t* out_counts, uint64_t run_capacity, uint64_t* out_num_runs,
                             pgpu_query_stats* out_stats, pgpu_table_layout* out_layout);
+
+/* ---- HyperLogLog sketches: DISTINCTCOUNTHLL / DISTINCTCOUNTRAWHLL ---------------------------------------------------
+ * The reference keeps the column's dictionary ids per group and offers dictionary.get(id) to a HyperLogLog only when
+ * the result is extracted (DistinctCountHLLAggregationFunction.java:104-110,176-184,438-447), so the sketch of group g
+ * is a function of the occupancy of section 0 of the table GROUP BY g_1..g_n, c along cid (key = g + inner * cid).
+ * The caller hashes the global dictionary of c once into a LUT, lut[cid] = j | r << 16: register j = h >>> (32 - log2m)
+ * and rank r = nlz((h << log2m) | ((1 << (log2m - 1)) + 1)) + 1 of the value's 32-bit hash h.  The stage raises, per
+ * occupied cell (count > 0, the fold's test), register j of g to r:
+ *   regs  uint32[inner_keys x W]  group g's W = pgpu_hll_words(log2m) words at g * W; register p is the 5 bits of word
+ *                                 p / 6 at bit 5 * (p mod 6) -- RegisterSet's layout, so that int32 log2m, int32 4 * W
+ *                                 and the words, all big-endian, are HyperLogLog.getBytes().  A key without an occupied
+ *                                 cell keeps W zero words.
+ * The maximum is commutative: the result does not depend on scheduling.
+ * pgpu_table_hll enqueues the fold (dev_out, out_bytes: exactly as pgpu_table_fold writes it -- the stage appends no
+ * section) and the sketches on `stream` without synchronising, for dense and one-word hash input as pgpu_table_fold
+ * takes them; temporary memory comes from the context's pool in stream order.  dev_lut (num_values entries) and
+ * dev_regs (inner_keys x W words) are device memory.
+ * Precondition: every occupied cid is below num_values and every LUT entry has j < 2^log2m and r <= 31.  A cell whose
+ * cid is num_values or more reads no LUT entry and offers nothing, and an entry outside those bounds is skipped, so
+ * that nothing is read or stored outside the arrays whatever the table and the LUT hold; for such input the sketches
+ * no longer cover the cells the fold counted.  Every table and LUT the runtime's callers build meet it.
+ *   PGPU_E_INVALID     : as pgpu_fold_layout_of; log2m outside PGPU_HLL_MIN_LOG2M..PGPU_HLL_MAX_LOG2M; a NULL
+ *                        argument; num_values = 0; out_bytes too small
+ *   PGPU_E_UNSUPPORTED : as pgpu_fold_layout_of; inner_keys x W x 4 bytes above PGPU_HLL_MAX_BYTES (a cap, not a
+ *                        property of the kernels) */
+#define PGPU_HLL_MIN_LOG2M 4
+#define PGPU_HLL_MAX_LOG2M 16
+#define PGPU_HLL_MAX_BYTES (1ull << 30)
+/* W: RegisterSet's int32 words for 2^log2m registers (43 for 8, 683 for 12); 0 outside 4..16. */
+uint32_t pgpu_hll_words(int32_t log2m);
+int pgpu_table_hll(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
+                   uint64_t inner_keys, const uint32_t* dev_lut, uint64_t num_values, int32_t log2m, void* dev_out,
+                   uint64_t out_bytes, void* dev_regs);
+/* pgpu_query_collect_fold plus the sketches of the returned rows, for a query submitted with PGPU_Q_FOLD: waits
+ * (PGPU_E_CANCELLED / PGPU_E_TIMEOUT pass through with nothing folded), stages `lut` -- HOST memory, num_values
+ * entries, read before the call returns -- through pinned memory, folds and sketches, and compacts every non-empty key
+ * of the folded table ascending by g (out_keys, out_cells = capacity x folded num_sections) with that row's W words
+ * (out_regs = capacity x W).  There is no `order`: an ORDER BY on the estimate is the host's, and a trim would only
+ * save bytes.
+ * When capacity is too small the call returns PGPU_E_INVALID with the needed count in *out_num_groups, writes no rows
+ * and KEEPS the query: call again with larger buffers, or call pgpu_query_release.  Every other outcome releases the
+ * query, as pgpu_query_collect_runs does. */
+int pgpu_query_collect_hll(pgpu_query* query, uint64_t inner_keys, const uint32_t* lut, uint64_t num_values,
+                           int32_t log2m, int64_t* out_keys, int64_t* out_cells, uint64_t capacity,
+                           uint64_t* out_num_groups, uint32_t* out_regs, pgpu_query_stats* out_stats,
+                           pgpu_table_layout* out_layout);
 
 /* Single-GPU asynchronous form (the combine operator of one server: BaseCombineOperator.getNextBlock submits the
  * segments' work and blocks in mergeResults, core/operator/combine/BaseCombineOperator.java:79-146):

@@ -48,6 +48,8 @@ PGPU_FIXED_TOL_BITS = 40
 PGPU_FOLD_MAX_KEYS = 1 << 26  # most inner keys of a fold (pgpu_fold_layout_of)
 PGPU_SELECT_MAX = 8  # most percentiles of one selection (pgpu_select_layout_of)
 PGPU_MODE_MIN, PGPU_MODE_MAX, PGPU_MODE_AVG = 1, 2, 4  # reducer mask of a mode reduction (pgpu_mode_layout_of)
+PGPU_HLL_MIN_LOG2M, PGPU_HLL_MAX_LOG2M = 4, 16  # log2m of a HyperLogLog stage (pgpu_table_hll)
+PGPU_HLL_MAX_BYTES = 1 << 30  # most bytes of its registers
 ABI_VERSION = 13
 
 
@@ -270,6 +272,12 @@ SIGNATURES = [
                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                           C.POINTER(C.c_int64), C.c_uint64, C.POINTER(C.c_uint64),
                                           C.POINTER(QueryStats), C.POINTER(TableLayout)]),
+    ("pgpu_hll_words", C.c_uint32, [C.c_int32]),
+    ("pgpu_table_hll", C.c_int, [_P, C.POINTER(TableLayout), _P, _P, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
+                                 C.c_int32, _P, C.c_uint64, _P]),
+    ("pgpu_query_collect_hll", C.c_int, [_P, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.c_int32,
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_uint64, C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint32), C.POINTER(QueryStats), C.POINTER(TableLayout)]),
     ("pgpu_query_submit", C.c_int, [_P, C.POINTER(QueryDesc), C.POINTER(_P)]),
     ("pgpu_query_collect", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_uint64,
                                      C.POINTER(C.c_uint64), C.POINTER(QueryStats)]),

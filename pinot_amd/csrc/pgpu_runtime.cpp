@@ -88,6 +88,12 @@ hipError_t pgpu_launch_mode(const int64_t* in, uint64_t N, int32_t nsec, bool ha
 size_t pgpu_runs_temp_bytes(uint64_t N, bool hash, uint64_t inner, int num_cus);
 hipError_t pgpu_launch_runs_count(const int64_t* in, uint64_t N, int32_t nsec, bool hash, uint64_t inner,
                                   uint64_t* offsets, void* temp, size_t temp_bytes, int num_cus, hipStream_t st);
+// HyperLogLog sketches of the same table, and the rows of the compacted keys gathered from them (pgpu_hll.hip)
+uint32_t pgpu_hll_words_of(int32_t log2m);
+hipError_t pgpu_launch_hll(const int64_t* in, uint64_t N, int32_t nsec, bool hash, uint64_t inner, const uint32_t* lut,
+                           uint64_t num_values, int32_t log2m, uint32_t* regs, int num_cus, hipStream_t st);
+hipError_t pgpu_launch_hll_gather(const uint32_t* regs, const int64_t* keys, uint64_t n, uint64_t inner, int32_t log2m,
+                                  uint32_t* out, hipStream_t st);
 hipError_t pgpu_launch_runs_emit(const int64_t* in, uint64_t N, int32_t nsec, bool hash, uint64_t inner,
                                  const uint64_t* offsets, uint32_t* cids, int64_t* counts, uint64_t cap, void* temp,
                                  size_t temp_bytes, int num_cus, hipStream_t st);
@@ -342,6 +348,9 @@ struct Workspace {
   DevMem mode_vals;                    // pgpu_query_collect_mode: the column's values
   DevMem runs_off, runs_cids, runs_counts;  // pgpu_query_collect_runs: the value runs of the query's table
   PinnedMem h_runs_total;              // ... their number, read between the count and the emit
+  DevMem hll_lut, hll_regs, hll_keys, hll_rows;  // pgpu_query_collect_hll: the LUT, every key's words, the returned
+                                       // keys and their rows
+  PinnedMem h_hll_lut;                 // ... the caller's LUT, staged for the copy to hll_lut
   PinnedMem h_arena, h_stats, h_total, h_table, h_segcnt, h_leafbits, h_segany, h_fsment;
   PinnedMem h_fold;                    // pgpu_query_collect_fold: a small folded table, compacted on the host
   PinnedMem h_mode_vals;               // pgpu_query_collect_mode: the caller's values, staged for the copy to mode_vals
@@ -5218,15 +5227,15 @@ int pgpu_table_topk(pgpu_context* ctx, const pgpu_table_layout* layout, const vo
 
 // ---- DISTINCTCOUNT, PERCENTILE, MODE: the fold of a GROUP BY g, c table over c, the rank selection and the mode -----
 // reduction behind it, or the value runs of the table beside it (include/pinot_gpu.h; kernels in pgpu_fold.hip,
-// pgpu_select.hip, pgpu_mode.hip, pgpu_runs.hip).  The eleven entry points state what they were asked for as a
-// FoldedSpec and share one layout builder (folded_layout), one size of temporary memory (folded_temp_bytes) and one
-// enqueue (enqueue_folded).
+// pgpu_select.hip, pgpu_mode.hip, pgpu_runs.hip), or the HyperLogLog sketches of its occupied cells (pgpu_hll.hip).
+// The thirteen entry points state what they were asked for as a FoldedSpec and share one layout builder
+// (folded_layout), one size of temporary memory (folded_temp_bytes) and one enqueue (enqueue_folded).
 namespace {
 
 // Which public contract is served: the stage names the last step asked for, not what the numbers happen to be -- a
 // selection of 0 percentiles or a mode reduction with an empty mask is refused as such, never run as the step before.
-enum FoldedStage { STAGE_FOLD, STAGE_SELECT, STAGE_MODE, STAGE_RUNS };
-const char* const kStageTable[] = {"folded", "selected", "mode", "runs"};
+enum FoldedStage { STAGE_FOLD, STAGE_SELECT, STAGE_MODE, STAGE_RUNS, STAGE_HLL };
+const char* const kStageTable[] = {"folded", "selected", "mode", "runs", "folded"};
 
 struct FoldedSpec {
   FoldedStage stage = STAGE_FOLD;
@@ -5242,7 +5251,13 @@ struct FoldedSpec {
   bool selects() const { return stage == STAGE_SELECT || (stage == STAGE_MODE && num_percentiles != 0); }
   bool modes() const { return stage == STAGE_MODE; }
   bool avg() const { return modes() && (reducers & PGPU_MODE_AVG) != 0; }
+  const uint32_t* lut = nullptr;        // STAGE_HLL: uint32[num_values] (j | r << 16 per cid) ...
+  bool lut_on_device = false;           // ... in device memory (pgpu_table_hll) or the caller's host memory
+  int32_t log2m = 0;
+  uint32_t* regs = nullptr;             // STAGE_HLL: uint32[inner_keys x W] in device memory
+
   bool runs() const { return stage == STAGE_RUNS; }  // (its table is the folded one: nothing is appended to it)
+  bool hll() const { return stage == STAGE_HLL; }    // (likewise)
 };
 
 // The layout of the resulting table and where the stages write in it: sections [0, picks_at - 1) are the input's,
@@ -5277,6 +5292,9 @@ int folded_layout(const pgpu_table_layout& in, const FoldedSpec& s, FoldedLayout
   if (s.selects() && (k < 1 || k > PGPU_SELECT_MAX))
     return fail(PGPU_E_INVALID, "%d percentiles (1..%d are selected at once)", k, PGPU_SELECT_MAX);
   const uint64_t inner_keys = s.inner_keys;
+  if (s.hll() && pgpu_hll_words_of(s.log2m) == 0)
+    return fail(PGPU_E_INVALID, "HyperLogLog log2m %d (%d..%d are served)", s.log2m, PGPU_HLL_MIN_LOG2M,
+                PGPU_HLL_MAX_LOG2M);
   if (inner_keys == 0) return fail(PGPU_E_INVALID, "fold over 0 inner keys");
   if (in.num_sections < 1 || in.num_sections > PGPU_MAX_SECTIONS)
     return fail(PGPU_E_INVALID, "table of %d sections", in.num_sections);
@@ -5289,6 +5307,9 @@ int folded_layout(const pgpu_table_layout& in, const FoldedSpec& s, FoldedLayout
     return fail(PGPU_E_UNSUPPORTED, "fold into %llu keys (more than a collect returns)", (unsigned long long)inner_keys);
   if (in.num_sections + 1 > PGPU_MAX_SECTIONS)
     return fail(PGPU_E_UNSUPPORTED, "no section left for the distinct count (%d in use)", in.num_sections);
+  if (s.hll() && inner_keys * (uint64_t)pgpu_hll_words_of(s.log2m) * 4 > PGPU_HLL_MAX_BYTES)
+    return fail(PGPU_E_UNSUPPORTED, "HyperLogLog registers of %llu keys at log2m %d exceed %llu bytes",
+                (unsigned long long)inner_keys, s.log2m, (unsigned long long)PGPU_HLL_MAX_BYTES);
   int entry = first_free_entry(in);
   if (entry >= 16) return fail(PGPU_E_UNSUPPORTED, "no aggregation entry left for the distinct count");
   pgpu_table_layout& F = out->layout;
@@ -5342,6 +5363,10 @@ int check_operands(const FoldedSpec& s) {
   }
   if (s.avg() && (!s.values || s.num_values == 0))
     return fail(PGPU_E_INVALID, "PGPU_MODE_AVG without the column's values");
+  // (one stage per spec: a FoldedSpec names a selection, a mode reduction or runs by being of another stage)
+  if (s.hll() && (s.num_percentiles != 0 || s.reducers != 0 || s.run_offsets))
+    return fail(PGPU_E_INVALID, "HyperLogLog sketches together with a selection, a mode reduction or value runs");
+  if (s.hll() && (!s.lut || s.num_values == 0)) return fail(PGPU_E_INVALID, "HyperLogLog sketches without the column's LUT");
   return PGPU_OK;
 }
 
@@ -5372,6 +5397,11 @@ int enqueue_folded(const pgpu_table_layout& in, const void* table, const FoldedS
     e = pgpu_launch_runs_count(t, in.num_keys, in.num_sections, hash, s.inner_keys, s.run_offsets, temp, temp_bytes,
                                num_cus, st);
     if (e != hipSuccess) return fail(PGPU_E_HIP, "table runs: %s", hipGetErrorString(e));
+  }
+  if (s.hll()) {
+    e = pgpu_launch_hll(t, in.num_keys, in.num_sections, hash, s.inner_keys, s.lut, s.num_values, s.log2m, s.regs,
+                        num_cus, st);
+    if (e != hipSuccess) return fail(PGPU_E_HIP, "table hll: %s", hipGetErrorString(e));
   }
   if (s.selects()) {
     e = pgpu_launch_select(t, in.num_keys, in.num_sections, hash, s.inner_keys, s.percentiles, s.num_percentiles, o,
@@ -5435,7 +5465,23 @@ int fold_on_workspace(pgpu_query* qq, FoldedSpec& s, const FoldedLayout& fl, siz
   if (rc == PGPU_OK && s.stage != STAGE_FOLD) {
     e = ws->fold_tmp.ensure(tb + 16, qq->ctx->mpool, ws->stream);
     if (e != hipSuccess)
-      rc = fail(PGPU_E_HIP, "table %s: %s", s.runs() ? "runs" : (s.modes() ? "mode" : "select"), hipGetErrorString(e));
+      rc = fail(PGPU_E_HIP, "table %s: %s", s.hll() ? "hll" : (s.runs() ? "runs" : (s.modes() ? "mode" : "select")),
+                hipGetErrorString(e));
+  }
+  if (rc == PGPU_OK && s.hll() && !s.lut_on_device) {
+    // the caller's LUT is read here, into pinned memory the copy to the device may outlive this call from
+    const size_t lb = 4 * (size_t)s.num_values;
+    e = ws->h_hll_lut.ensure(lb);
+    if (e == hipSuccess) e = ws->hll_lut.ensure(lb, qq->ctx->mpool, ws->stream);
+    if (e == hipSuccess) e = ws->hll_regs.ensure(4 * s.inner_keys * (size_t)pgpu_hll_words_of(s.log2m), qq->ctx->mpool, ws->stream);
+    if (e == hipSuccess) {
+      memcpy(ws->h_hll_lut.p, s.lut, lb);
+      e = hipMemcpyAsync(ws->hll_lut.p, ws->h_hll_lut.p, lb, hipMemcpyHostToDevice, ws->stream);
+    }
+    if (e != hipSuccess) rc = fail(PGPU_E_HIP, "table hll: %s", hipGetErrorString(e));
+    s.lut = (const uint32_t*)ws->hll_lut.p;
+    s.lut_on_device = true;
+    s.regs = (uint32_t*)ws->hll_regs.p;
   }
   if (rc == PGPU_OK && s.avg() && !s.values_on_device) {
     // the caller's values are read here, into pinned memory the copy to the device may outlive this call from
@@ -5641,6 +5687,85 @@ int collect_runs(pgpu_query* qq, uint64_t inner_keys, int64_t* out_keys, int64_t
   return rc;
 }
 
+// pgpu_table_hll: pgpu_table_fold with the sketches beside it.
+int table_hll(pgpu_context* ctx, const pgpu_table_layout* in, const void* dev_table, void* stream, uint64_t inner_keys,
+              const uint32_t* dev_lut, uint64_t num_values, int32_t log2m, void* dev_out, uint64_t out_bytes,
+              void* dev_regs) {
+  if (!dev_regs) return fail(PGPU_E_INVALID, "null argument");
+  FoldedSpec s{STAGE_HLL, inner_keys};
+  s.lut = dev_lut;
+  s.lut_on_device = true;
+  s.num_values = num_values;
+  s.log2m = log2m;
+  s.regs = (uint32_t*)dev_regs;
+  return table_folded(ctx, in, dev_table, stream, s, dev_out, out_bytes);
+}
+
+// pgpu_query_collect_hll: the wait, the fold and the sketches on the query's workspace, the non-empty keys compacted,
+// their rows of words gathered on the device and copied out.  Too small a capacity keeps the query for another call;
+// every other outcome releases it.
+int collect_hll(pgpu_query* qq, uint64_t inner_keys, const uint32_t* lut, uint64_t num_values, int32_t log2m,
+                int64_t* out_keys, int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups, uint32_t* out_regs,
+                pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
+  if (!qq || !qq->tws) return fail(PGPU_E_INVALID, "query was not submitted");
+  if (!out_num_groups) {
+    pgpu_query_release(qq);
+    return fail(PGPU_E_INVALID, "null argument");
+  }
+  // (a cancelled or timed-out query returns here: nothing is folded.  A second call on a kept query waits again,
+  // which returns at once, and folds again: the query's table is only read)
+  int rc = pgpu_query_wait(qq, out_stats);
+  FoldedSpec s{STAGE_HLL, inner_keys};
+  s.lut = lut;
+  s.num_values = num_values;
+  s.log2m = log2m;
+  FoldedLayout fl;
+  const pgpu_table_layout& F = fl.layout;
+  Workspace* ws = qq->ws;
+  const uint32_t W = pgpu_hll_words_of(log2m);
+  size_t tb = 0;
+  uint64_t n = 0;
+  bool keep = false;
+  if (rc == PGPU_OK) rc = folded_layout(qq->layout, s, &fl);
+  if (rc == PGPU_OK) rc = check_operands(s);
+  if (rc == PGPU_OK) rc = fold_on_workspace(qq, s, fl, &tb);
+  if (rc == PGPU_OK) {
+    if (pgpu_table_bytes(&F) <= (8u << 20)) {
+      // (rows are counted first and written only when they fit)
+      rc = fetch_small_folded(qq, F);
+      if (rc == PGPU_OK) {
+        n = small_folded_rows(qq, F, nullptr, nullptr, 0);
+        if (n <= capacity) small_folded_rows(qq, F, out_keys, out_cells, capacity);
+      }
+    } else {
+      rc = compact_into(qq->ctx, ws, &F, ws->fold.p, ws->stream, out_keys, out_cells, capacity, &n);
+      if (rc == PGPU_E_INVALID && n > capacity) rc = PGPU_OK;  // its only refusal here: more rows than room (below)
+    }
+    *out_num_groups = n;
+    if (rc == PGPU_OK && n > capacity) {
+      keep = true;
+      rc = fail(PGPU_E_INVALID, "%llu non-empty groups exceed capacity %llu", (unsigned long long)n,
+                (unsigned long long)capacity);
+    }
+  }
+  if (rc == PGPU_OK && n && (!out_keys || !out_regs)) rc = fail(PGPU_E_INVALID, "null argument");
+  if (rc == PGPU_OK && n) {
+    // the rows of the returned keys: the keys go back to the device, their words are gathered there and come out whole
+    hipError_t e = ws->hll_keys.ensure(8 * n, qq->ctx->mpool, ws->stream);
+    if (e == hipSuccess) e = ws->hll_rows.ensure(4 * n * (size_t)W, qq->ctx->mpool, ws->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ws->hll_keys.p, out_keys, 8 * n, hipMemcpyHostToDevice, ws->stream);
+    if (e == hipSuccess)
+      e = pgpu_launch_hll_gather((const uint32_t*)ws->hll_regs.p, (const int64_t*)ws->hll_keys.p, n, inner_keys, log2m,
+                                 (uint32_t*)ws->hll_rows.p, ws->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_regs, ws->hll_rows.p, 4 * n * (size_t)W, hipMemcpyDeviceToHost, ws->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
+    if (e != hipSuccess) rc = fail(PGPU_E_HIP, "hll rows copy: %s", hipGetErrorString(e));
+  }
+  if (rc == PGPU_OK && out_layout) *out_layout = F;
+  if (!keep) pgpu_query_release(qq);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -5672,6 +5797,20 @@ int pgpu_table_mode(pgpu_context* ctx, const pgpu_table_layout* in_layout, const
                     const double* dev_values, uint64_t num_values, void* dev_out, uint64_t out_bytes) {
   const FoldedSpec s{STAGE_MODE, inner_keys, percentiles, num_percentiles, reducers, dev_values, num_values, true};
   return table_folded(ctx, in_layout, dev_table, stream, s, dev_out, out_bytes);
+}
+
+uint32_t pgpu_hll_words(int32_t log2m) { return pgpu_hll_words_of(log2m); }
+int pgpu_table_hll(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,
+                   uint64_t inner_keys, const uint32_t* dev_lut, uint64_t num_values, int32_t log2m, void* dev_out,
+                   uint64_t out_bytes, void* dev_regs) {
+  return table_hll(ctx, in_layout, dev_table, stream, inner_keys, dev_lut, num_values, log2m, dev_out, out_bytes,
+                   dev_regs);
+}
+int pgpu_query_collect_hll(pgpu_query* qq, uint64_t inner_keys, const uint32_t* lut, uint64_t num_values, int32_t log2m,
+                           int64_t* out_keys, int64_t* out_cells, uint64_t capacity, uint64_t* out_num_groups,
+                           uint32_t* out_regs, pgpu_query_stats* out_stats, pgpu_table_layout* out_layout) {
+  return collect_hll(qq, inner_keys, lut, num_values, log2m, out_keys, out_cells, capacity, out_num_groups, out_regs,
+                     out_stats, out_layout);
 }
 
 int pgpu_table_runs(pgpu_context* ctx, const pgpu_table_layout* in_layout, const void* dev_table, void* stream,

@@ -35,8 +35,9 @@ from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
 from ._lib import PGPU_DOUBLE, PGPU_E_UNSUPPORTED, PGPU_FLOAT, PGPU_INT, PGPU_LONG, PGPU_STRING, UnsupportedPlanError
-from .distinct import (FOLDED, ValueList, ValueMap, ValueSet, merge_runs, runs_mode, runs_percentile, value_key,
-                       value_order)
+from .distinct import (FOLDED, SKETCHED, ValueList, ValueMap, ValueSet, merge_runs, runs_mode, runs_percentile,
+                       value_key, value_order)
+from .hll import HyperLogLog
 from .query import QueryContext, java_double_string
 
 VERSION_3 = 3
@@ -58,6 +59,7 @@ _KEY_ORDINAL = {name: i for i, (name, _) in enumerate(METADATA_KEYS)}
 
 OBJECT_TYPE_AVG_PAIR = 4  # ObjectSerDeUtils.ObjectType.AvgPair
 OBJECT_TYPE_DOUBLE_ARRAY_LIST = 3
+OBJECT_TYPE_HYPER_LOG_LOG = 6  # ObjectSerDeUtils.ObjectType.HyperLogLog: hll.getBytes()
 # stored type -> (ObjectType value, struct format of an element / key); a set's elements, a map's keys
 _SET_TYPES = {PGPU_INT: (9, "i"), PGPU_LONG: (15, "q"), PGPU_FLOAT: (16, "f"), PGPU_DOUBLE: (17, "d"),
               PGPU_STRING: (18, None)}
@@ -72,6 +74,8 @@ def object_bytes(v) -> bytes:
         if 4 + n > MAX_CELL_BYTES:
             raise UnsupportedPlanError(PGPU_E_UNSUPPORTED, f"an OBJECT cell of {4 + n} bytes (a Java array holds "
                                                            f"{MAX_CELL_BYTES})")
+    if isinstance(v, HyperLogLog):
+        return struct.pack(">i", OBJECT_TYPE_HYPER_LOG_LOG) + v.to_bytes()
     if isinstance(v, ValueSet):
         otype, fmt = _SET_TYPES[v.stored_type]
         if fmt is None:  # Set<String>: int length + UTF-8 bytes per element
@@ -100,6 +104,8 @@ def object_from_bytes(var: bytes, off: int):
     (otype,) = struct.unpack_from(">i", var, off)
     if otype == OBJECT_TYPE_AVG_PAIR:
         return struct.unpack_from(">dq", var, off + 4)
+    if otype == OBJECT_TYPE_HYPER_LOG_LOG:
+        return HyperLogLog.from_bytes(var, off + 4)
     (n,) = struct.unpack_from(">i", var, off + 4)
     pos = off + 8
     for stored, (t, fmt) in _SET_TYPES.items():
@@ -354,6 +360,9 @@ def _agg_column(a, result_name: bool) -> Tuple[str, str]:
     -- distinctCount_c, percentile95_c or percentile95.5_c (PercentileAggregationFunction.java:59-70), mode_c --,
     DOUBLE otherwise (getIntermediateResultColumnType)."""
     fn = a.function
+    if fn in SKETCHED:  # distinctCountHLL_c / distinctCountRawHLL_c, an OBJECT (the sketch) for both
+        return (a.result_name if result_name else
+                f"{'distinctCountHLL' if fn == 'DISTINCTCOUNTHLL' else 'distinctCountRawHLL'}_{a.column}"), OBJECT
     if fn in FOLDED:
         if result_name:
             return a.result_name, OBJECT
@@ -418,6 +427,8 @@ def _merge(fn: str, a, b):
     """AggregationFunction.merge of two intermediate results.  DISTINCTCOUNT: the union of the sets with fastutil's key
     equality (floatToIntBits / doubleToLongBits: one NaN, -0.0 apart from 0.0); PERCENTILE: the lists concatenated
     (their runs united); MODE: the maps merged by Long::sum (ModeAggregationFunction.java:425-455)."""
+    if fn in SKETCHED:
+        return a.merge(b)
     if fn == "DISTINCTCOUNT":
         uniq = {value_key(v): v for v in list(a.values) + list(b.values)}
         return ValueSet(sorted(uniq.values(), key=value_order), a.stored_type)
@@ -438,6 +449,8 @@ def _final(fn: str, v, agg=None):
     """AggregationFunction.extractFinalResult (agg: the aggregation itself, for a percentile or a mode's reducer).
     DISTINCTCOUNT: the set's size as an INT; PERCENTILE: the sorted list at pgpu_select.hip's select_rank, -inf when
     empty; MODE: the reducers of ModeAggregationFunction.java:486-672, -inf when empty."""
+    if fn in SKETCHED:  # the estimate as a LONG; the raw form's serialised sketch as lowercase hex
+        return v.to_bytes().hex() if fn == "DISTINCTCOUNTRAWHLL" else v.cardinality()
     if fn == "DISTINCTCOUNT":
         return len(v.values)
     if fn == "PERCENTILE":
@@ -467,7 +480,7 @@ class BrokerResult:
 def reduce_data_tables(query: QueryContext, tables: Sequence[DataTable]) -> BrokerResult:
     """GroupByDataTableReducer / AggregationDataTableReducer over the servers' DataTables."""
     from .plan import order_and_limit, to_select_order
-    folded = [i for i, a in enumerate(query.aggregations) if a.function in FOLDED]
+    folded = [i for i, a in enumerate(query.aggregations) if a.function in FOLDED or a.function in SKETCHED]
     ngc = len(query.group_by)
     _refuse_distinct(query, all(t.schema is None or all(t.schema.column_types[ngc + i] == OBJECT for i in folded)
                                 for t in tables))
@@ -504,7 +517,8 @@ def reduce_data_tables(query: QueryContext, tables: Sequence[DataTable]) -> Brok
         if inter is None:  # no server had a row: the functions' empty results
             inter = [{"COUNT": 0, "COUNTMV": 0, "MIN": math.inf, "MINMV": math.inf, "MAX": -math.inf,
                       "MAXMV": -math.inf, "AVG": (0.0, 0), "AVGMV": (0.0, 0), "DISTINCTCOUNT": ValueSet([], PGPU_INT),
-                      "PERCENTILE": ValueList([], []), "MODE": ValueMap([], [], PGPU_INT)}.get(fn, 0.0) for fn in fns]
+                      "PERCENTILE": ValueList([], []), "MODE": ValueMap([], [], PGPU_INT)}.get(fn, 0.0)
+                     if fn not in SKETCHED else HyperLogLog.empty(a.log2m) for fn, a in zip(fns, aggs)]
         res.rows = [to_select_order(query, tuple(_final(fn, v, a) for fn, v, a in zip(fns, inter, aggs)))]
         return res
     finals = [values[k] + tuple(_final(fn, v, a) for fn, v, a in zip(fns, merged[k], aggs)) for k in merged]

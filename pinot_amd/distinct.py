@@ -43,7 +43,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 from . import _lib
 from ._lib import UnsupportedPlanError
-from .query import MODE_REDUCERS, MV_AGGS, AggregationSpec, OrderByExpr, QueryContext
+from .query import HLL_AGGS, MODE_REDUCERS, MV_AGGS, AggregationSpec, OrderByExpr, QueryContext
 
 UNLIMITED = 1 << 62
 DISTINCT = "DISTINCTCOUNT"
@@ -51,16 +51,22 @@ PERCENTILE = "PERCENTILE"
 MODE = "MODE"
 FOLDED = (DISTINCT, PERCENTILE, MODE)  # the functions answered from the table folded over their column
 MODE_BITS = {"MIN": _lib.PGPU_MODE_MIN, "MAX": _lib.PGPU_MODE_MAX, "AVG": _lib.PGPU_MODE_AVG}
+HLL, RAWHLL = HLL_AGGS
+SKETCHED = HLL_AGGS  # the functions answered from the HyperLogLog registers raised beside the fold (pinot_amd/hll.py)
 
 
 def has_distinct(query: QueryContext) -> bool:
-    return any(a.function in FOLDED for a in query.aggregations)
+    return any(a.function in FOLDED or a.function in SKETCHED for a in query.aggregations)
+
+
+def has_sketches(query: QueryContext) -> bool:
+    return any(a.function in SKETCHED for a in query.aggregations)
 
 
 def folded_names(query: QueryContext) -> str:
     """The folded functions a query holds, for messages: 'DISTINCTCOUNT', 'PERCENTILE', 'MODE' or several of them as
     'DISTINCTCOUNT / PERCENTILE'."""
-    return " / ".join(f for f in FOLDED if any(a.function == f for a in query.aggregations))
+    return " / ".join(f for f in FOLDED + SKETCHED if any(a.function == f for a in query.aggregations))
 
 
 def _unsupported(why: str) -> UnsupportedPlanError:
@@ -81,6 +87,10 @@ class DistinctPass:
     percentile: List[int] = field(default_factory=list)  # original indexes of PERCENTILE(column, p), one pick each
 
     mode: List[int] = field(default_factory=list)  # original indexes of MODE(column, reducer), every reducer
+    # a sketch pass (collected through pgpu_query_collect_hll; distinct, percentile and mode are empty then): original
+    # indexes of DISTINCTCOUNTHLL(column, log2m) / DISTINCTCOUNTRAWHLL(column, log2m), and their log2m
+    sketch: List[int] = field(default_factory=list)
+    log2m: int = 0
 
     @property
     def reducers(self) -> int:
@@ -107,13 +117,23 @@ def lower(query: QueryContext) -> List[DistinctPass]:
         raise _unsupported(f"{what} in a query with FILTER(WHERE ...) aggregations")
     if any(a.function in MV_AGGS for a in query.aggregations):
         raise _unsupported(f"{what} together with *MV aggregations")
-    plain = [i for i, a in enumerate(query.aggregations) if a.function not in FOLDED]
+    plain = [i for i, a in enumerate(query.aggregations) if a.function not in FOLDED and a.function not in SKETCHED]
     by_col: Dict[str, Tuple[List[int], List[int], List[int]]] = {}
+    sketches: Dict[str, List[int]] = {}
     for i, a in enumerate(query.aggregations):
-        if a.function in FOLDED:
+        if a.function in FOLDED or a.function in SKETCHED:
             if a.column in query.group_by:
                 raise _unsupported(f"{a.function} of the group column {a.column!r}")
+        if a.function in FOLDED:
             by_col.setdefault(a.column, ([], [], []))[FOLDED.index(a.function)].append(i)
+        elif a.function in SKETCHED:
+            from .hll import check_log2m
+            check_log2m(a.log2m)
+            mine = sketches.setdefault(a.column, [])
+            if mine and query.aggregations[mine[0]].log2m != a.log2m:
+                raise _unsupported(f"{a.function} of {a.column!r} with log2m {a.log2m} beside log2m "
+                                   f"{query.aggregations[mine[0]].log2m}: one sketch size per column and query")
+            mine.append(i)
     passes = []
     for k, (col, (idx, pidx, midx)) in enumerate(by_col.items()):
         if len(pidx) > _lib.PGPU_SELECT_MAX:
@@ -132,6 +152,20 @@ def lower(query: QueryContext) -> List[DistinctPass]:
         folded = QueryContext(table=query.table, select=groups + faggs, aggregations=faggs, filter=query.filter,
                               group_by=groups, order_by=[], limit=UNLIMITED, options=dict(query.options))
         passes.append(DistinctPass(low, folded, col, list(mine), idx, pidx, midx))
+    # a sketch of c is a pass of its own, whatever else the query asks of c: the same Q', its folded table as the fold
+    # leaves it (the stage appends no section), the registers beside it.  HLL and RAWHLL of one column share it.
+    for col, sidx in sketches.items():
+        mine = plain if not passes else []
+        aggs = [query.aggregations[i] for i in mine] or [AggregationSpec("COUNT", None)]
+        groups = list(query.group_by)
+        low = QueryContext(table=query.table, select=groups + [col] + aggs, aggregations=list(aggs),
+                           filter=query.filter, group_by=groups + [col], order_by=[], limit=UNLIMITED,
+                           options=dict(query.options))
+        faggs = list(aggs) + [AggregationSpec(DISTINCT, col)]
+        folded = QueryContext(table=query.table, select=groups + faggs, aggregations=faggs, filter=query.filter,
+                              group_by=groups, order_by=[], limit=UNLIMITED, options=dict(query.options))
+        passes.append(DistinctPass(low, folded, col, list(mine), [], sketch=sidx,
+                                   log2m=query.aggregations[sidx[0]].log2m))
     return passes
 
 
@@ -145,6 +179,10 @@ def order_pass(query: QueryContext, passes: Sequence[DistinctPass]) -> Optional[
     if not query.group_by or not query.order_by:
         return None
     ob = query.order_by[0]
+    if any(ob.expression == query.aggregations[i].result_name for p in passes for i in p.sketch):
+        return None  # ORDER BY a sketch's estimate: every group returns and the host orders (a trim only saves bytes)
+    if passes[0].sketch:
+        return None  # only sketch passes (the exact ones come first), whose collect takes no order: likewise
     if ob.aggregation is not None and ob.aggregation.function == MODE:
         if ob.aggregation.reducer == "AVG":
             raise _unsupported(f"ORDER BY MODE({ob.aggregation.column}, 'AVG'): the trim on the device orders by a "
@@ -171,18 +209,47 @@ def _join_stats(query: QueryContext, results: Sequence):
     return st
 
 
+@dataclass
+class PassSketches:
+    """What one sketch pass's pgpu_query_collect_hll brought back: the folded rows decoded (a QueryResult of the pass's
+    plain aggregations + DISTINCTCOUNT(column), groups ascending by key) and the register words of those rows."""
+    result: object          # QueryResult
+    words: object           # uint32 [rows][W]
+    log2m: int
+
+    def sketch(self, row: int):
+        """The HyperLogLog of a row; row < 0 (no doc matched): the empty sketch."""
+        from .hll import HyperLogLog
+        return HyperLogLog.empty(self.log2m) if row < 0 else HyperLogLog(self.log2m, self.words[row].copy())
+
+
+def place_sketches(query: QueryContext, p: DistinctPass, sketch, fin: list, inter: Optional[list] = None) -> None:
+    """The finals of a sketch pass's functions: the estimate as a LONG, for the raw form the lowercase hex of the
+    serialised sketch (SerializedHLL.java:39-41); their intermediate is the sketch."""
+    for i in p.sketch:
+        fin[i] = sketch.to_bytes().hex() if query.aggregations[i].function == RAWHLL else sketch.cardinality()
+        if inter is not None:
+            inter[i] = sketch
+
+
 def raise_result(query: QueryContext, passes: Sequence[DistinctPass], results: Sequence):
     """The original query's QueryResult from the passes' folded results (QueryResults of ``DistinctPass.folded``; a pass
-    with percentiles or modes carries the global dictionary of its column as ``value_dictionary``)."""
+    with percentiles or modes carries the global dictionary of its column as ``value_dictionary``; a sketch pass comes
+    as PassSketches)."""
     from .plan import QueryResult, order_and_limit, to_select_order
 
+    sketches = [r if isinstance(r, PassSketches) else None for r in results]
+    results = [r.result if isinstance(r, PassSketches) else r for r in results]
     res = QueryResult(query=query, stats=_join_stats(query, results))
     na = len(query.aggregations)
     dicts = {id(p): r.value_dictionary for p, r in zip(passes, results) if p.percentile or p.mode}
 
-    def place(fin: list, p: DistinctPass, vals: Sequence) -> None:
+    def place(fin: list, p: DistinctPass, vals: Sequence, sk=None, row: int = -1) -> None:
         for j, i in enumerate(p.plain):
             fin[i] = vals[j]
+        if p.sketch:
+            place_sketches(query, p, sk.sketch(row), fin)
+            return
         nm = sum(a.function == MODE for a in p.folded.aggregations)
         nd = len(vals) - 1 - len(p.percentile) - nm  # plain aggregations, the distinct count, the picks, the modes
         for i in p.distinct:
@@ -203,22 +270,22 @@ def raise_result(query: QueryContext, passes: Sequence[DistinctPass], results: S
 
     if not query.group_by:
         fin: list = [None] * na
-        for p, r in zip(passes, results):
-            place(fin, p, r.aggregation_result)
+        for p, r, sk in zip(passes, results, sketches):
+            place(fin, p, r.aggregation_result, sk, 0 if sk is not None and len(sk.words) else -1)
         res.aggregation_result = fin
         res.rows = [to_select_order(query, tuple(fin))]
         return res
     ng = len(query.group_by)
-    others = [{tuple(r[:ng]): r[ng:] for r in rr.group_rows} for rr in results[1:]]
+    # (a sketch pass's rows are ascending by key, as its words: the row of a group is its position)
+    index = [{tuple(r[:ng]): k for k, r in enumerate(rr.group_rows)} for rr in results]
     rows = []
     for r in results[0].group_rows:
         key = tuple(r[:ng])
-        if not all(key in m for m in others):
+        if not all(key in m for m in index[1:]):
             continue  # trimmed away by the pass that carries the ORDER BY expression
         fin = [None] * na
-        place(fin, passes[0], r[ng:])
-        for p, m in zip(passes[1:], others):
-            place(fin, p, m[key])
+        for p, rr, m, sk in zip(passes, results, index, sketches):
+            place(fin, p, rr.group_rows[m[key]][ng:], sk, m[key])
         rows.append(key + tuple(fin))
     res._group_rows = rows
     res.rows = [to_select_order(query, r) for r in order_and_limit(query, rows)]
@@ -342,9 +409,12 @@ def raise_runs(query: QueryContext, passes: Sequence[DistinctPass], runs: Sequen
     na = len(query.aggregations)
     ng = len(query.group_by)
 
-    def place(fin: list, inter: list, p: DistinctPass, pr: PassRuns, row: int, vals: Sequence, ivals: Sequence) -> None:
+    def place(fin: list, inter: list, p: DistinctPass, pr, row: int, vals: Sequence, ivals: Sequence) -> None:
         for j, i in enumerate(p.plain):
             fin[i], inter[i] = vals[j], ivals[j]
+        if p.sketch:  # (pr: PassSketches)
+            place_sketches(query, p, pr.sketch(row), fin, inter)
+            return
         lo, hi = (int(pr.offsets[row]), int(pr.offsets[row + 1])) if row >= 0 else (0, 0)
         d = pr.dictionary
         ids = pr.cids[lo:hi]
@@ -369,7 +439,7 @@ def raise_runs(query: QueryContext, passes: Sequence[DistinctPass], runs: Sequen
     if not ng:
         fin, inter = [None] * na, [None] * na
         for p, pr in zip(passes, runs):
-            nrows = len(pr.offsets) - 1
+            nrows = len(pr.words) if p.sketch else len(pr.offsets) - 1
             place(fin, inter, p, pr, 0 if nrows else -1, pr.result.aggregation_result, pass_intermediate(pr.result)[()])
         res.aggregation_result = fin
         res._intermediate = {(): inter}

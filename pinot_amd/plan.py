@@ -43,7 +43,7 @@ from .predicate import (DictPredicateEvaluator, RawPredicateEvaluator, SortedDic
                         get_raw_predicate_evaluator)
 from .query import (MV_AGGS, UNBOUNDED, AggregationSpec, FilterContext, QueryContext, row_index,
                     split_filtered_aggregations)
-from .distinct import FOLDED, folded_names, has_distinct
+from .distinct import FOLDED, SKETCHED, folded_names, has_distinct, has_sketches
 from .segment import DOCID_COLUMN, GpuContext, GpuSegment
 
 AGG_FN = {"COUNT": PGPU_AGG_COUNT, "SUM": PGPU_AGG_SUM, "MIN": PGPU_AGG_MIN, "MAX": PGPU_AGG_MAX,
@@ -558,6 +558,7 @@ class GpuPlanMaker:
         # changes.
         self._prepared: Dict[tuple, tuple] = {}
         self._distinct: Dict[int, tuple] = {}  # id(query) -> (query, its DISTINCTCOUNT passes)
+        self._hll_luts: Dict[tuple, tuple] = {}  # (id(global dictionary), log2m) -> (the dictionary, its hll.lut)
         # execute_mergeable: the value runs a pass's first pgpu_query_collect_runs has room for (it is repeated once
         # with the count the library asks for)
         self.run_capacity = 1 << 22
@@ -935,6 +936,10 @@ class GpuPlanMaker:
         for p, (prep, inner, F, order) in zip(passes, ready):
             pq = self._launch(prep, segments)
             pq.fold = FoldedPass(inner, F, p.folded, p.percentiles, p.reducers)
+            if p.sketch:
+                pq.fold.log2m = p.log2m
+                pq.fold.lut = self.hll_lut(prep[4][-1][0], segments[0].column(p.column).data_type if segments else PGPU_INT,
+                                           p.log2m)
             pq.order = order
             pending.append(pq)
         return DistinctPending(self, query, passes, pending)
@@ -960,6 +965,56 @@ class GpuPlanMaker:
             ready.append((prep, inner, F, order))
         return ready
 
+    def hll_lut(self, dictionary, stored_type: int, log2m: int) -> np.ndarray:
+        """hll.lut of a global dictionary, computed once per (dictionary object, log2m): the plan maker hands the same
+        dictionary object to every query over the same segments (global_dictionary), and its LUT lives with it."""
+        from . import hll
+        key = (id(dictionary), log2m)
+        hit = self._hll_luts.get(key)
+        if hit is not None and hit[0] is dictionary:
+            return hit[1]
+        if len(self._hll_luts) >= 32:
+            self._hll_luts.clear()
+        lut = hll.lut(dictionary, stored_type, log2m)
+        self._hll_luts[key] = (dictionary, lut)
+        return lut
+
+    def _collect_hll(self, pending: "PendingQuery"):
+        """One sketch pass through pgpu_query_collect_hll: its folded rows (the plain aggregations and the distinct count)
+        and the register words of its column per row.  Every non-empty key comes back: the capacity is the inner key
+        space, so that the call is not repeated."""
+        from .distinct import PassSketches
+        from . import hll
+        lib = self.ctx._lib
+        fold = pending.fold
+        F = fold.layout
+        W = hll.num_words(fold.log2m)
+        cap = int(min(F.num_keys, 1 << 26))
+        keys = np.empty(max(cap, 1), dtype=np.int64)
+        cells = np.empty((max(cap, 1), F.num_sections), dtype=np.int64)
+        n, st = C.c_uint64(), QueryStats()
+        lut = np.ascontiguousarray(fold.lut, dtype=np.uint32)
+        h, pending.handle = pending.handle, None
+        # (the words of the returned rows only: a first call without room for them asks for the count and keeps the
+        # query, so that a wide key space with few groups does not allocate cap x W words)
+        words = np.empty((0, W), dtype=np.uint32)
+        rc = _lib.PGPU_E_INVALID
+        for room in ((64, cap) if cap * W * 4 > (64 << 20) else (cap,)):
+            words = np.empty((max(room, 1), W), dtype=np.uint32)
+            rc = lib.pgpu_query_collect_hll(h, fold.inner_keys, lut.ctypes.data_as(C.POINTER(C.c_uint32)), len(lut),
+                                            fold.log2m, keys.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            cells.ctypes.data_as(C.POINTER(C.c_int64)), room, C.byref(n),
+                                            words.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st), None)
+            if not (rc == _lib.PGPU_E_INVALID and n.value > room):  # (too small: the query is kept)
+                break
+        else:
+            lib.pgpu_query_release(h)
+        _lib.check(rc)
+        table = GroupTable(keys[: n.value], cells[: n.value], F)
+        gdicts = [g[0] for g in pending.globals_]
+        res = finish(fold.query, table, gdicts[:-1], self._stats_of(st, fold.query, pending))
+        return PassSketches(res, words[: n.value], fold.log2m)
+
     def collect_distinct(self, pending: "DistinctPending") -> QueryResult:
         """Collect every pass (also after one failed: each owns a query handle) and join them."""
         results, err = [], None
@@ -981,6 +1036,10 @@ class GpuPlanMaker:
         # NonScanBasedAggregationOperator answers DISTINCTCOUNT from the dictionary (AggregationPlanNode.java:185-197):
         # the scanned segments' tables come back unfolded -- their rows are the value sets -- and are united on the
         # host with the non-scan segments' dictionaries
+        if has_sketches(query):
+            # the scanned segments' sketches come back through the mergeable execution and take the non-scan segments'
+            # dictionaries there (sketch_non_scan)
+            return self.execute_mergeable(query, segments)
         rest = [s for s, ns in zip(segments, non_scan) if not ns]
         meta = [s for s, ns in zip(segments, non_scan) if ns]
         if not rest:
@@ -1009,6 +1068,8 @@ class GpuPlanMaker:
             return mv_raise(query, parts, self.collect(pending))
         L = pending.layout
         fold = pending.fold
+        if fold is not None and fold.log2m:  # a sketch pass: the folded rows and their HyperLogLog registers
+            return self._collect_hll(pending)
         if fold is not None:  # a DISTINCTCOUNT pass: the rows of its table folded over the distinct column
             L = fold.layout
         cap = int(min(L.num_keys, 1 << 26))
@@ -1084,7 +1145,7 @@ class GpuPlanMaker:
         runs, err = [], None
         for pq in pending.pending:
             try:
-                runs.append(self._collect_runs(pq))
+                runs.append(self._collect_hll(pq) if pq.fold.log2m else self._collect_runs(pq))
             except _lib.PinotGpuError as e:
                 err = err or e
         pending.pending = []
@@ -1141,6 +1202,8 @@ class GpuPlanMaker:
         the host from the runs.  Any other query is execute()."""
         if not has_distinct(query):
             return self.execute(query, segments)
+        if has_sketches(query):
+            self.distinct_passes(query)  # (what the lowering refuses is refused on the non-scan plan as well)
         non_scan = self.non_scan_segments(query, segments)
         if not any(non_scan):
             return self.collect_mergeable(self.submit_mergeable(query, segments))
@@ -1163,6 +1226,8 @@ class GpuPlanMaker:
         res = merge_non_scan(query, scanned, meta, sets)
         for ai, vs in found.items():
             res._intermediate[()][ai] = vs
+        if has_sketches(query):
+            sketch_non_scan(query, scanned, meta, res)
         res.value_sets = True
         return res
 
@@ -1255,14 +1320,16 @@ class GpuPlanMaker:
         :171-195): a filter that folds to match-all plus only COUNT / MIN / MAX is answered from segment metadata
         and the dictionary, with no scan (NonScanBasedAggregationOperator)."""
         q = query
-        fns = ("COUNT", "MIN", "MAX", "MINMV", "MAXMV", "DISTINCTCOUNT")
+        fns = ("COUNT", "MIN", "MAX", "MINMV", "MAXMV", "DISTINCTCOUNT") + SKETCHED
         if q.group_by or q.has_filtered_aggregations or any(a.function not in fns for a in q.aggregations):
             return [False] * len(segments)
 
         def answers(s: GpuSegment, a: AggregationSpec) -> bool:
             if a.function == "COUNT":
                 return True
-            if a.function == "DISTINCTCOUNT":  # the dictionary's size: dictionary-encoded single-value columns only
+            if a.function == "DISTINCTCOUNT" or a.function in SKETCHED:
+                # the dictionary's size, or its values offered to the sketch (NonScanBasedAggregationOperator.java
+                # :106-115,204-211): dictionary-encoded single-value columns only
                 col = s.column(a.column)
                 return not col.is_raw and not col.is_mv and s.dictionaries.get(a.column) is not None
             return s.min_max(a.column) is not None
@@ -1279,6 +1346,8 @@ class FoldedPass:
     query: QueryContext  # the folded query: what the rows of that table answer
     percentiles: list  # picked behind the fold (pgpu_query_collect_select) ...
     reducers: int  # ... and the reducer mask of the mode reduction behind them (pgpu_query_collect_mode), 0: none
+    log2m: int = 0  # a sketch pass (pgpu_query_collect_hll): the sketch's size, 0: none ...
+    lut: Optional[np.ndarray] = None  # ... and hll.lut of the global dictionary of the pass's column
 
 
 @dataclass
@@ -1408,6 +1477,9 @@ def merge_non_scan(query: QueryContext, scanned: Optional[QueryResult], segments
                 keys |= value_keys(s.dictionaries[a.column])
             vals.append(len(keys))
             continue
+        if a.function in SKETCHED:  # (set by the caller, which holds the scanned segments' sketch: sketch_non_scan)
+            vals.append(None)
+            continue
         v = {"COUNT": 0, "MIN": math.inf, "MAX": -math.inf, "MINMV": math.inf, "MAXMV": -math.inf}[a.function] \
             if scanned is None else scanned.aggregation_result[ai]
         for s in segments:
@@ -1428,6 +1500,25 @@ def merge_non_scan(query: QueryContext, scanned: Optional[QueryResult], segments
     res._intermediate = {(): list(vals)}
     res.rows = [to_select_order(query, tuple(vals))]
     return res
+
+
+def sketch_non_scan(query: QueryContext, scanned: Optional[QueryResult], segments: Sequence[GpuSegment],
+                    res: QueryResult) -> None:
+    """The sketch functions of a partly non-scan aggregation-only query, into `res` (merge_non_scan's): the scanned
+    segments' sketch united with the sketch of every non-scan segment's dictionary, which is what offering each of its
+    values gives (NonScanBasedAggregationOperator.java:106-115,204-211) -- no launch for those segments."""
+    from . import hll
+    from .distinct import RAWHLL
+    for ai, a in enumerate(query.aggregations):
+        if a.function not in SKETCHED:
+            continue
+        hll.check_log2m(a.log2m)
+        sk = scanned.intermediate[()][ai] if scanned is not None else hll.HyperLogLog.empty(a.log2m)
+        for s in segments:
+            sk = sk.merge(hll.sketch_of(s.dictionaries[a.column], s.column(a.column).data_type, a.log2m))
+        res._intermediate[()][ai] = sk
+        res.aggregation_result[ai] = sk.to_bytes().hex() if a.function == RAWHLL else sk.cardinality()
+    res.rows = [to_select_order(query, tuple(res.aggregation_result))]
 
 
 def merge_filtered(query: QueryContext, parts, results: Sequence[QueryResult]) -> QueryResult:

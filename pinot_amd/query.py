@@ -46,13 +46,15 @@ class FilterContext:
 
 @dataclass(frozen=True)
 class AggregationSpec:
-    function: str        # COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT, PERCENTILE, MODE; COUNTMV, SUMMV, MINMV, MAXMV, AVGMV
-                         # (multi-value columns)
+    function: str        # COUNT, SUM, MIN, MAX, AVG, DISTINCTCOUNT, PERCENTILE, MODE, DISTINCTCOUNTHLL,
+                         # DISTINCTCOUNTRAWHLL; COUNTMV, SUMMV, MINMV, MAXMV, AVGMV (multi-value columns)
     column: Optional[str]  # None for COUNT(*)
     filter_key: Optional[str] = None  # FILTER(WHERE ...) clause text; its FilterContext is QueryContext.agg_filters
     percentile: Optional[float] = None  # PERCENTILE only: 0..100
     percentile_arg: bool = False        # written PERCENTILE(col, p), not PERCENTILE<N>(col): the result's name differs
     reducer: Optional[str] = None       # MODE only: MIN, MAX or AVG over several modes (MultiModeReducerType)
+    log2m: Optional[int] = None         # DISTINCTCOUNTHLL / DISTINCTCOUNTRAWHLL only: the sketch's size (not in the name:
+                                        # getResultColumnName gives distinctcounthll(col) whatever it is)
 
     @property
     def result_name(self) -> str:
@@ -157,6 +159,13 @@ _AGGS = {"COUNT", "SUM", "MIN", "MAX", "AVG", "DISTINCTCOUNT", "COUNTMV", "SUMMV
 _PERCENTILE = re.compile(r"^PERCENTILE(EST|TDIGEST|RAWEST|RAWTDIGEST|RAW)?(\d*)(MV)?$", re.IGNORECASE)
 MODE_REDUCERS = ("MIN", "MAX", "AVG")  # MultiModeReducerType
 MV_AGGS = {"COUNTMV": "COUNT", "SUMMV": "SUM", "MINMV": "MIN", "MAXMV": "MAX", "AVGMV": "AVG"}
+HLL_AGGS = ("DISTINCTCOUNTHLL", "DISTINCTCOUNTRAWHLL")
+DEFAULT_LOG2M = 8  # CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M (CommonConstants.java:85)
+# the sketch functions that are not served, refused by name
+_HLL_REFUSED = {"DISTINCTCOUNTHLLMV": "over single-value columns only", "DISTINCTCOUNTRAWHLLMV": "over single-value "
+                "columns only", "DISTINCTCOUNTSMARTHLL": "the smart form starts as an exact set: only DISTINCTCOUNTHLL and "
+                "DISTINCTCOUNTRAWHLL are served", "FASTHLL": "a derived-column sketch: only DISTINCTCOUNTHLL and "
+                "DISTINCTCOUNTRAWHLL are served"}
 
 
 class SqlError(ValueError):
@@ -233,6 +242,10 @@ class _Parser:
             return self.percentile_item(t[1].upper(), pm)
         if t[0] == "id" and t[1].upper() in ("MODE", "MODEMV") and t2 == ("op", "("):
             return self.mode_item(t[1].upper())
+        if t[0] == "id" and t[1].upper() in _HLL_REFUSED and t2 == ("op", "("):
+            raise SqlError(f"{t[1].upper()} is not supported ({_HLL_REFUSED[t[1].upper()]})")
+        if t[0] == "id" and t[1].upper() in HLL_AGGS and t2 == ("op", "("):
+            return self.hll_item(t[1].upper())
         if t[0] == "id" and t[1].upper() in _AGGS and t2 == ("op", "("):
             fn = t[1].upper()
             self.i += 2
@@ -311,6 +324,27 @@ class _Parser:
         if nxt[0] == "id" and nxt[1].upper() == "FILTER":
             raise SqlError("MODE with FILTER(WHERE ...) is not supported")
         return AggregationSpec("MODE", col, reducer=reducer)
+
+    def hll_item(self, name: str) -> AggregationSpec:
+        """DISTINCTCOUNTHLL(col) or DISTINCTCOUNTHLL(col, log2m) with log2m an integer literal, 8 when absent
+        (DistinctCountHLLAggregationFunction.java:60-75); DISTINCTCOUNTRAWHLL likewise.  Which log2m are served is the
+        planner's matter (an unserved one keeps the CPU plan), not the parser's."""
+        self.i += 2
+        col = self.ident()
+        log2m = DEFAULT_LOG2M
+        if self.op(","):
+            t = self.peek()
+            if t[0] not in ("num", "str") or not re.fullmatch(r"-?\d+", t[1]):
+                raise SqlError(f"{name}: log2m is an integer literal, not {t[1]}")
+            self.i += 1
+            log2m = int(t[1])
+            if self.peek() == ("op", ","):
+                raise SqlError(f"{name} takes a column and at most log2m")
+        self.expect_op(")")
+        nxt = self.peek()
+        if nxt[0] == "id" and nxt[1].upper() == "FILTER":
+            raise SqlError(f"{name} with FILTER(WHERE ...) is not supported")
+        return AggregationSpec(name, col, log2m=log2m)
 
     def order_item(self) -> OrderByExpr:
         item = self.select_item()
